@@ -14,8 +14,9 @@ N > 1   : weak scaling, one rank per GPU: every rank owns a 2297-image gallery s
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel class = the 16-bit MFMA GEMM -- fp16 operands by default, the
 reference's own GPU precision -- measured live with HIP events on the launch stream inside the timed region; `frac` prices the
-class's ALGORITHMIC flops, `executed_tflop_per_step` says what the split-precision products add on top) and `cpu_baseline`
-(the fp32 CPU oracle on a bounded sample).
+class's ALGORITHMIC flops, `executed_tflop_per_step` says what the split-precision products add on top).  With --full the line
+also carries `cpu_baseline` (the fp32 CPU oracle on a bounded sample), `recall`, `extra` and `roofline.power`, each measured after
+the timed region.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 from __future__ import annotations
 
@@ -81,9 +82,13 @@ def kernel_source_sha() -> str:
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10, help="timed steps (the default N = 1 run also spends ~40 s AFTER the timed region on the `recall` object "
-                    "and ~15 s on `cpu_baseline`: --no-recall / --no-cpu-baseline skip them)")
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline does not need (N = 1): the `recall` "
+                    "object (~40 s), roofline.power (~6 s), the `extra` object (~15 s) and `cpu_baseline` (~15 s); each can still be skipped with its "
+                    "--no-* switch.  Without --full the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64): top-k scores and gallery indices, fused query vectors and image features of that step")
     ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16", "fp32", "fp8"], help="fp16: fp16 MFMA operands (the reference's GPU autocast precision; the bf16 rate); fp8: bf16 engine whose ViT qkv / fc1 / fc2 GEMMs run on e4m3fn operands (BASELINE config C5)")
     ap.add_argument("--fp8-base", default="bf16", choices=["bf16", "fp16"], help="--dtype fp8: the 16-bit dtype of everything but the fp8 GEMMs (fp16: with the split-precision Q-Former)")
     ap.add_argument("--fp8-layers", default="all", choices=["all", "mlp"], help="--dtype fp8: which ViT GEMMs take e4m3 operands: qkv + fc1 + fc2, or fc1 + fc2 only")
@@ -99,20 +104,25 @@ def parse():
                     "double-buffered); instrumented steps (--prof-every) stay serialised")
     ap.add_argument("--qf-group", type=int, default=1, help="G: the Q-Former stage (gallery-side pass, query fusion, ranking) of G consecutive steps runs once, "
                     "on their G x 128 images and G x 233 queries; the ViT still runs per step on batches of 128 (1 = every step on its own)")
-    ap.add_argument("--no-recall", action="store_true", help="skip the `recall` object (default ON at N = 1: after the timed region, Recall@1/5/10/50 + subset "
+    ap.add_argument("--no-recall", action="store_true", help="skip the `recall` object (ON under --full at N = 1: after the timed region, Recall@1/5/10/50 + subset "
                     "recalls of the benchmarked engine on the planted-structure CIRR-val-sized case next to the UNMODIFIED REFERENCE's own scores for "
                     "every 22nd query of that case -- 191 queries x 2297 images, tests/golden/planted_c2_subset_eva*.npz; ~40 s; synthetic weights: "
                     "the real checkpoint is a network fetch)")
     ap.add_argument("--no-power", action="store_true", help="skip roofline.power (socket power + shader clock from rocm-smi over ~6 s of extra un-timed steps "
                     "after the timed region, N = 1)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` object (default ON for the default N = 1 fp16 ViT-g line: config C5's per-GPU encode step -- "
+    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` object (ON under --full for the N = 1 fp16 ViT-g line: config C5's per-GPU encode step -- "
                     "ViT-L backbone, fp8 MFMA, 20 timed steps -- measured by a second invocation of this script after the timed region, ~15 s)")
-    ap.add_argument("--recall", action="store_true", help="(accepted for compatibility: the recall object is on by default)")
+    ap.add_argument("--recall", action="store_true", help="(accepted for compatibility: the recall object is on under --full)")
     ap.add_argument("--cpu-images", type=int, default=32, help="size of the bounded CPU-baseline sample (~15 s of CPU work on 16 cores)")
     ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full"], help="full: ONLY run SURVEY.md section 8(d)'s CPU-baseline procedure -- config C1's "
                     "sizes (256 gallery images, 64 queries), one warm-up + best of 3, all host cores (~10 min) -- print it as one JSON line and write "
                     "gpurun_out/cpu_baseline_c1.json; no GPU work, no bench line (once per round -> profiles/rNN_cpu_baseline_c1.json)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not a.full:                                           # a plain run: the headline only
+        a.no_recall = a.no_power = a.no_extra = a.no_cpu_baseline = True
+    return a
 
 
 def usable_cores() -> int:
@@ -199,6 +209,21 @@ def cpu_baseline_full(cfg, n_img: int = 256, nq: int = 64, reps: int = 3):
             "combined": f"1 / (s per image + {QUERIES}/{GALLERY} x s per query): the workload's query : image ratio"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: {name: device tensor} -> DIR/<name>.npy, floating data as float32, integer data as float64 (exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64) for k, v in arrays.items()}
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES}-byte limit")
+    for k, x in host.items():
+        np.save(os.path.join(path, f"{k}.npy"), x)
+
+
 def respawn(n: int) -> int:
     """`bench.py --gpus N` outside a launcher: start N ranks of this script under torch.distributed.run (one per GPU;
     rank r on GPU r, or r % visible GPUs when fewer are visible -- see `backend` in main)."""
@@ -243,12 +268,15 @@ def c5_slice(a, dev, rank, world):
     from sprc_amd.dist import ShardedRanker
     # the library's ranking path: local scores in blocks of QB query rows (a 1-GB budget), never the 5-GB [10 000, 125 000] matrix
     ranker = ShardedRanker(shard, index_base=0, sim_budget_bytes=QB * N_SHARD * 4)
+    last = {}                                                # --dump-outputs: what the latest step computed
 
     def step(i):
         eng.vit_forward(images, out=raw)
         feats, f16 = eng.qformer_image(raw)
         lo = (i * BATCH) % (N_SHARD - BATCH)
         shard[lo:lo + BATCH].copy_(f16 if f16 is not None and f16.dtype == torch.bfloat16 else feats)
+        if a.dump_outputs:
+            last["image_feats"] = feats
 
     def fuse_and_rank():
         for s in range(0, NQ_LOCAL, 250):
@@ -265,6 +293,8 @@ def c5_slice(a, dev, rank, world):
         step(a.warmup + i)
     torch.cuda.synchronize()
     t_step = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
     t0 = time.perf_counter()
     fuse_and_rank()
     torch.cuda.synchronize()
@@ -471,6 +501,11 @@ def main():
     raws = torch.empty((NBUF, G * BATCH, cfg.vit.tokens, cfg.vit.width), dtype=torch.float32, device=dev)
     done = [torch.cuda.Event() for _ in range(NBUF)] if pipe else None
     groups = [0]                                                                  # groups run so far: the parity of the raw buffers
+    last = {}                                                                     # --dump-outputs: what the latest group computed
+
+    def keep(n: int, feats, fusion, out):
+        if a.dump_outputs:
+            last.update(n=n, feats=feats, fusion=fusion, out=out)
 
     def qformer_stage(buf, first: int, n: int, serial: bool):
         """gallery-side pass for the n x 128 images in buf, fusion of their n x 233 queries, ranking (on the current stream(s))"""
@@ -486,13 +521,16 @@ def main():
         if side is not None and not serial:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                image_side().record_stream(side)
+                feats = image_side()
+                feats.record_stream(side)
             fusion, _ = eng.qformer_fuse(refs, ids_g[:nq], mask_g[:nq])           # R6 fusion half
             main.wait_stream(side)
         else:
-            image_side()
+            feats = image_side()
             fusion, _ = eng.qformer_fuse(refs, ids_g[:nq], mask_g[:nq])
-        return ranker.rank(fusion, TOPK)                                          # R6 similarity + R7 top-k (+ exchanges)
+        out = ranker.rank(fusion, TOPK)                                           # R6 similarity + R7 top-k (+ exchanges)
+        keep(n, feats, fusion, out)
+        return out
 
     def group_pipelined(first: int, n: int):
         g = groups[0]
@@ -517,6 +555,7 @@ def main():
             s_fuse.wait_stream(s_img)                                             # the ranking reads the gallery slices of this group
             out = ranker.rank(fusion, TOPK)
             done[g % NBUF].record(s_fuse)
+        keep(n, feats, fusion, out)
         return out
 
     def drain():
@@ -560,6 +599,12 @@ def main():
     drain()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        # the last STEP of the last group (its last 128 images and 233 queries); the gathered top-k rows are in rank order
+        vals, idx = last["out"][0], last["out"][1]
+        rows = lambda t: t.reshape(-1, last["n"] * Q_PER_STEP, t.shape[-1])[:, -Q_PER_STEP:].reshape(-1, t.shape[-1])
+        dump_outputs(a.dump_outputs, {"topk_scores": rows(vals), "topk_indices": rows(idx), "fusion": last["fusion"][-Q_PER_STEP:],
+                                      "image_feats": last["feats"][-BATCH:]})
     n_prof = max(n_prof, 1)
     power = None
     if world == 1 and not use_dist and not a.no_power:

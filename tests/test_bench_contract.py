@@ -1,7 +1,9 @@
-"""The bench line the driver parses: the committed `profiles/r06_bench_n1.json` (an unedited `python bench.py` line; its
+"""The bench line the driver parses: the committed `profiles/r06_bench_n1.json` (an unedited `python bench.py --full` line; its
 `roofline.traffic` is what bench.py itself reads from profiles/r06_traffic.json) must carry every field of the measurement contract,
 and the roofline numbers must be self-consistent and agree with the committed rocprofv3 summaries of the same build."""
 import json
+import subprocess
+import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -61,7 +63,7 @@ def test_committed_bench_line_follows_the_contract():
 
 def test_committed_default_line_carries_the_power_reading():
     """`roofline.power` (round 6): rocm-smi socket power + shader clock over extra un-timed steps; the part sits near its 1400-W cap far below the
-    2.4 GHz the 2.5 PF peak assumes -- profiles/r06_bench_default_line.json is an unedited default `python bench.py` line."""
+    2.4 GHz the 2.5 PF peak assumes -- profiles/r06_bench_default_line.json is an unedited `python bench.py --full` line."""
     d = json.loads((ROOT / "profiles" / "r06_bench_default_line.json").read_text())
     pw = d["roofline"]["power"]
     assert pw["samples"] >= 3 and 1000 < pw["socket_w_mean"] <= pw["socket_w_max"] <= 1450 and 1200 < pw["sclk_mhz_mean"] < 2400
@@ -113,3 +115,14 @@ def test_same_box_dtype_comparison_is_on_record():
     f16, b16, single = (json.loads((ROOT / "profiles" / f"r06_bench_n1{t}.json").read_text()) for t in ("", "_bf16", "_fp16_single"))
     assert f16["dtype"] == "fp16" and b16["dtype"] == "bf16" and single["dtype"] == "fp16"
     assert b16["value"] > single["value"] > f16["value"] > 0.85 * b16["value"]
+
+
+def test_bench_options_parse_without_a_gpu():
+    """A plain run measures the headline only; --full adds the objects measured after the timed region; --dump-outputs DIR writes the last
+    timed step's outputs; --steps sets the timed steps and must be positive.  Argument parsing needs no GPU."""
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    for opt in ("--full", "--dump-outputs", "--steps", "--warmup", "--gpus"):
+        assert opt in p.stdout, opt
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr

@@ -14,7 +14,7 @@ cd $R
 bash tools/profile_bench.sh r03/pb --pipeline 0 --qf-streams 1 > $O/profile_bench.log 2>&1      # one stream: a kernel's duration is its own
 cp $O/pb/kernel_stats.csv $O/bench_kernel_stats.csv; cp $O/pb/traffic.json $O/traffic.json
 cp $O/traffic.json profiles/r03_traffic.json        # bench.py reads roofline.traffic from here (same box, same kernel sources)
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.log 2>&1; tail -1 $O/bench_n1.log > $O/bench_n1.json
+python bench.py --steps 20 --warmup 5 --full > $O/bench_n1.log 2>&1; tail -1 $O/bench_n1.log > $O/bench_n1.json
 python bench.py --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n1_bf16.json
 SPRC_X3_OFF=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n1_fp16_single.json
 bash tools/pmc_kernel.sh r03/pmc "gemm_anti=gemm_anti_kernel,gemm_128=gemm_kernel,attention=attn_,layernorm=layernorm_kernel" -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --qf-streams 1 > $O/pmc.log 2>&1

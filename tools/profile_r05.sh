@@ -19,7 +19,7 @@ cd $R
 bash tools/profile_bench.sh r05/pb --pipeline 0 --qf-streams 1 --no-recall > $O/profile_bench.log 2>&1      # one stream: a kernel's duration is its own
 cp $O/pb/kernel_stats.csv $O/bench_kernel_stats.csv; cp $O/pb/traffic.json $O/traffic.json
 cp $O/traffic.json profiles/r05_traffic.json        # bench.py reads roofline.traffic from here (same box, same kernel sources)
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.log 2>&1; tail -1 $O/bench_n1.log > $O/bench_n1.json
+python bench.py --steps 20 --warmup 5 --full > $O/bench_n1.log 2>&1; tail -1 $O/bench_n1.log > $O/bench_n1.json
 python bench.py --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline --no-recall 2>/dev/null | tail -1 > $O/bench_n1_bf16.json
 SPRC_X3_OFF=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recall 2>/dev/null | tail -1 > $O/bench_n1_fp16_single.json
 for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recall 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['step_frac'])"; done > $O/bench_repeat.txt
