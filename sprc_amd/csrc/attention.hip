@@ -16,9 +16,6 @@
 #include <type_traits>
 
 #include "common.hpp"
-#ifndef SPRC_ATTN_NT
-#define SPRC_ATTN_NT 0
-#endif
 
 namespace sprc {
 
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bf16_kernel(AttnParams p) {
     constexpr int KROW = DHP * 2 + 16;        // bytes per K row in LDS
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, half = lane >> 5;
-    int b, h;                                 // all heads of an image on one XCD (block i runs on XCD i % 8): see attn_stream_kernel
+    int b, h;                                 // all heads of an image on one XCD (block i runs on XCD i % 8): see attn_dma_kernel
     if ((p.B & 7) == 0) { const int x = blockIdx.x & 7, i = blockIdx.x >> 3; h = i % p.H; b = (i / p.H) * 8 + x; }
     else { b = blockIdx.x / p.H; h = blockIdx.x % p.H; }
     const int Tkp = (p.Tk + 31) & ~31;
@@ -281,301 +278,49 @@ __global__ __launch_bounds__(64 * NW) void attn_bf16_kernel(AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Streaming bf16 kernel for long query axes (the ViT blocks: Tq = Tk = 257).  The resident-K/V kernel above needs
-// 110 KB of LDS for a ViT-g head, i.e. ONE workgroup per CU: its 60 us of staging per layer never overlapped its 144 us
-// of compute.  Here a workgroup is 3 waves = 96 queries of one (image, head) and walks the keys in 32-key tiles that are
-// double-buffered in LDS (2 x 13.5 KB): global loads of tile t+1 are issued before the MFMAs of tile t and written to
-// the other buffer afterwards (register staging, one barrier per tile), so five workgroups fit on a CU (LDS 27 KB,
-// <= 128 VGPRs) and one workgroup's loads, softmax VALU and stores run under its neighbours' MFMAs.
-// The three workgroups of an (image, head) re-stream the same K/V: the block index is remapped so that they run
-// back to back on ONE XCD (block b runs on XCD b % 8) and the re-reads hit that XCD's L2.
+// Streaming kernel for long query axes (the ViT blocks: Tq = Tk = 257).  The resident-K/V kernel above needs 110 KB of LDS
+// for a ViT-g head, i.e. ONE workgroup per CU: its 60 us of staging per layer never overlapped its 144 us of compute.  Here a
+// workgroup is NW waves = 32 NW queries of one (image, head) and walks the keys in 32-key tiles through a ring of NBUF tiles in
+// LDS, so several workgroups fit on a CU and one workgroup's loads, softmax VALU and stores run under its neighbours' MFMAs.
 // Same math as above: S^T = K.Q^T (a lane owns one query column), online softmax in the exp2 domain, O^T = V^T.P^T with P
-// kept in registers; V is transposed on its way into LDS (two keys per 32-bit write).
-// VALU diet (PMC on the first version: 20 VALU instructions per MFMA, the waves 50 % in s_waitcnt): (1) the padded-key mask
-// only exists in the code of the LAST tile; (2) with head_dim 88 in a 96-row V^T tile, row 88 holds ones, so the softmax
-// denominator falls out of the P.V MFMAs (no 16 adds per tile, and it is rescaled with O); (3) the running max only moves
-// when a tile's max exceeds it by more than 2^RESCALE_LOG2 (guide T13): P then stays <= 256 -- exact in fp32 accumulation,
-// same relative precision in bf16 -- and the 48-multiply rescale of O runs in the first tile and rarely after;
+// kept in registers.  VALU diet (PMC on the first streaming kernel: 20 VALU instructions per MFMA, the waves 50 % in s_waitcnt):
+// (1) the padded-key mask only exists in the code of the LAST tile; (2) with head_dim 88 in a 96-row V^T tile, row 88 holds
+// ones, so the softmax denominator falls out of the P.V MFMAs (no 16 adds per tile, and it is rescaled with O); (3) the running
+// max only moves when a tile's max exceeds it by more than 2^RESCALE_LOG2 (guide T13): P then stays <= 256 -- exact in fp32
+// accumulation, same relative precision in bf16 -- and the 48-multiply rescale of O runs in the first tile and rarely after;
 // (4) global addresses of a thread's pieces advance by a constant per tile.
 constexpr float RESCALE_LOG2 = 8.0f;
 
-// Bounds-checked 16-B loads through a raw buffer descriptor (non-template helpers: this hipcc drops the host stub of a kernel
+// Bounds-checked loads through a raw buffer descriptor (non-template helpers: this hipcc drops the host stub of a kernel
 // TEMPLATE whose dependent code calls the buffer builtins directly).  A lane whose offset lies outside [0, bytes - 16] reads
 // zeros: padded keys, the zero columns of the 96-wide tile and idle lanes need NO branch -- every load of a tile is
 // straight-line code, so the compiler can count them (`s_waitcnt vmcnt(N)`) instead of draining the queue at each branch
-// (which had serialised the double-buffered prefetch: one exposed ~2-us round trip per key tile).
+// (which had serialised the double-buffered prefetch of the first streaming kernel: one exposed ~2-us round trip per key tile).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t attn_rsrc(const char* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, bytes, 0x00020000);
 }
-__device__ __forceinline__ u32x4 attn_load16(__amdgpu_buffer_rsrc_t rs, uint32_t voffset) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voffset, 0, 0));
-}
 constexpr uint32_t ATTN_OOB = 0x80000000u;   // beyond every descriptor's range (an image's K/V rows span < 2 GiB)
 
-template <int DHP, bool ONES, int NW, bool F16, bool ABLATE = false>
-__global__ __launch_bounds__(64 * NW, 3) void attn_stream_kernel(AttnParams p, int nqb, int xcd_map, int debug_arg) {
-    // the production instantiation folds every ablation branch away: a run-time branch around the loads or the tile math makes
-    // the compiler merge its wait counters at the join and drain the whole load queue there
-    const int debug = ABLATE ? debug_arg : 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = 64 * NW, KS = DHP / 16, DT = DHP / 32, CPR = DHP / 8;
-    constexpr int KROW = DHP * 2 + 16;        // bytes per K row in LDS (conflict-free ds_read_b128 across 32 rows)
-    constexpr int VROW = 32 * 2 + 8;          // bytes per V^T row of one 32-key tile
-    constexpr int KBYTES = 32 * KROW, BUF = KBYTES + DHP * VROW;
-    constexpr int KPT = (32 * CPR + NT - 1) / NT;              // 16-B K pieces per thread per tile
-    static_assert(16 * CPR <= NT, "one (key pair, chunk) item of V per thread");
-    static_assert(NW * 32 * (DHP * 2 + 16) <= 160 * 1024, "output strips fit in LDS");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r32 = lane & 31, half = lane >> 5;
-    // Block b runs on XCD b % 8.  A token row of the packed qkv tensor holds the K (V) slices of ALL heads back to back
-    // (176 B each for ViT-g: not a multiple of the 128-B line), so neighbouring heads share cache lines: all heads and
-    // query blocks of one image are placed on ONE XCD, consecutively, and every fetched line is used by that XCD's L2
-    // (heads spread over the XCDs fetched 457 MB per launch against 300 MB of distinct bytes).
-    int b, h, qb;
-    if (xcd_map == 2) { const int x = blockIdx.x & 7, i = blockIdx.x >> 3; qb = i % nqb; h = (i / nqb) % p.H; b = (i / (nqb * p.H)) * 8 + x; }
-    else if (xcd_map == 1) { const int x = blockIdx.x & 7, i = blockIdx.x >> 3; qb = i % nqb; const int bh = (i / nqb) * 8 + x; b = bh / p.H; h = bh % p.H; }
-    else { const int bh = blockIdx.x / nqb; qb = blockIdx.x % nqb; b = bh / p.H; h = bh % p.H; }
-    const int dh = p.dh;
-    const int nkt = (p.Tk + 31) >> 5;
-    const bool ragged = (p.Tk & 31) != 0;
-
-    // ---- this thread's share of a tile: KPT 16-B pieces of K, one (key pair, 8-wide chunk) item of V ----
-    // descriptors cover this (image, head): rows [0, Tk) of head_dim*2 valid bytes each (the last row bounds the range)
-    const __amdgpu_buffer_rsrc_t rs_k = attn_rsrc(p.k + ((int64_t)b * p.Tk * p.ldk + (int64_t)h * dh) * 2,
-                                                  (uint32_t)((int64_t)(p.Tk - 1) * p.ldk * 2 + dh * 2));
-    const __amdgpu_buffer_rsrc_t rs_v = attn_rsrc(p.v + ((int64_t)b * p.Tk * p.ldv + (int64_t)h * dh) * 2,
-                                                  (uint32_t)((int64_t)(p.Tk - 1) * p.ldv * 2 + dh * 2));
-    uint32_t k_off[KPT];
-    int k_row[KPT], k_lds[KPT];
-#pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-        const int idx = tid + u * NT, c = idx % CPR;
-        k_row[u] = idx / CPR;
-        k_lds[u] = k_row[u] * KROW + c * 16;
-        // columns >= head_dim stay zero (pad of the 96-wide tile); rows >= 32 belong to no piece
-        k_off[u] = (k_row[u] < 32 && c * 8 < dh) ? (uint32_t)(k_row[u] * p.ldk * 2 + c * 16) : ATTN_OOB;
-    }
-    // consecutive lanes take consecutive 16-B chunks of ONE row (like K): with lanes running over the key pairs instead, a
-    // wave instruction touched 16 different rows (16-32 cache lines for 1 KB)
-    const int v_kp = tid / CPR, v_c = tid % CPR;
-    const bool v_item = v_kp < 16;
-    const bool v_ones = ONES && v_item && v_c * 8 == dh;         // this thread owns V^T rows dh .. dh+7: row dh = ones
-    // V^T rows are 18 dwords apart, so the eight rows of chunk c, c+4 and c+8 start on the same banks and the 32-bit
-    // transposing writes of a wave were 3-way conflicted (SQ_LDS_BANK_CONFLICT 45 % of the LDS cycles).  Key-pair column kp of
-    // rows 32..63 / 64..95 is stored at kp ^ 8 / kp ^ 4: at most 2-way (free for ds_write_b32); the fragment reads apply the
-    // same constant per 32-row tile (it permutes their four 8-byte pieces, at no cost).
-    const int v_col = (v_kp ^ (((v_c >> 2) & 1) * 8) ^ (((v_c >> 3) & 1) * 4)) * 4;
-    uint32_t v_off = (v_item && v_c * 8 < dh) ? (uint32_t)(v_kp * 2 * p.ldv * 2 + v_c * 16) : ATTN_OOB;
-    const uint32_t kstep = 32 * p.ldk * 2, vstep = 32 * p.ldv * 2, vnext = p.ldv * 2;
-    // Two staging register sets: the loads of tile t+2 are issued while tile t is computed and tile t+1 waits in the other
-    // set (ablation: with one set -- loads issued one tile ahead -- the kernel ran 175 us, 108 us with the loop's loads
-    // removed, 148 us with the MATH removed: a chain of nine exposed ~2-us memory round trips per workgroup).
-    struct Stage { u32x4 kreg[KPT], va, vb; };
-    Stage stg[2];
-    auto fetch = [&](Stage& g) {                                 // the next tile in key order: branch-free, rows >= Tk read zeros
-#pragma unroll
-        for (int u = 0; u < KPT; ++u) {
-            g.kreg[u] = attn_load16(rs_k, k_off[u]);
-            k_off[u] += kstep;
-        }
-        g.va = attn_load16(rs_v, v_off);
-        g.vb = attn_load16(rs_v, v_off + vnext);
-        v_off += vstep;
-    };
-    // issued unconditionally, also past the last tile (those rows read zeros at no memory cost): a branch around the loads
-    // makes the compiler drain the whole queue (`s_waitcnt vmcnt(0)`) where the paths join
-    auto fetch_any = [&](Stage& g, int) { fetch(g); };
-    auto commit = [&](Stage& g, int buf) {
-        u32x4 va = g.va, vb = g.vb;
-        char* sK = smem + buf * BUF;
-        char* sV = sK + KBYTES;
-#pragma unroll
-        for (int u = 0; u < KPT; ++u)
-            if (k_row[u] < 32) *reinterpret_cast<u32x4*>(sK + k_lds[u]) = g.kreg[u];
-        if (v_item) {
-            if (v_ones) va[0] = vb[0] = F16 ? 0x3c00u : 0x3f80u;  // 1.0 (fp16 / bf16) in row dh for both keys of the pair
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) {                     // rows (e, e+1) of the chunk: low / high halves of dword e/2
-                const uint32_t a = va[e >> 1], c = vb[e >> 1];
-                *reinterpret_cast<uint32_t*>(sV + (v_c * 8 + e) * VROW + v_col) = (a & 0xffffu) | (c << 16);
-                *reinterpret_cast<uint32_t*>(sV + (v_c * 8 + e + 1) * VROW + v_col) = (a >> 16) | (c & 0xffff0000u);
-            }
-        }
-    };
-    using std::false_type;
-    using std::true_type;
-    fetch_any(stg[0], 0);
-    fetch_any(stg[1], 1);
-
-    // Q^T fragments (B operand): lane (q = r32, half) holds Q[q][ks*16 + half*8 .. +8]
-    const int qt = qb * NW + wave;
-    const int qrow = min(qt * 32 + r32, p.Tq - 1);
-    const char* qptr = p.q + (((int64_t)b * p.Tq + qrow) * p.ldq + (int64_t)h * dh) * 2;
-    u32x4 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        const int d0 = ks * 16 + half * 8;
-        u32x4 val = {0u, 0u, 0u, 0u};
-        if (d0 < dh && !(debug & 32)) val = *reinterpret_cast<const u32x4*>(qptr + d0 * 2);
-        qf[ks] = val;
-    }
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-    const float sc = p.scale * LOG2E;
-
-    // one 32-key tile out of buffer kt & 1
-    auto tile = [&](int kt, auto tail_) {
-        constexpr bool TAIL = decltype(tail_)::value;
-        const char* sK = smem + (kt & 1) * BUF;
-        const char* sV = sK + KBYTES;
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        const char* krow = sK + r32 * KROW + half * 16;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            // (issuing all KS fragment reads ahead of the first MFMA through inline asm changed nothing: 124-127 us either way --
-            // with three waves per SIMD the other waves cover the read latency)
-            const u32x4 kf = *reinterpret_cast<const u32x4*>(krow + ks * 32);
-            s = mfma16<F16>(kf, qf[ks], s);
-        }
-        if constexpr (TAIL) {                   // padded keys: key of reg r = kt*32 + (r&3) + 8*(r>>2) + 4*half
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half >= p.Tk) s[r] = -INFINITY;
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * sc;            // every tile holds >= 1 real key: finite
-        if (__any(mx - m_run > RESCALE_LOG2)) {                  // always in the first tile (m_run = -inf), rarely afterwards
-            const float m_new = (mx - m_run > RESCALE_LOG2) ? mx : m_run;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);     // 1 for the queries that keep their max
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], sc, -m_run));
-        u32x4 pf[2];
-        float psum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[j][e] = pack16x2<F16>(s[8 * j + 2 * e], s[8 * j + 2 * e + 1]);
-                if constexpr (!ONES) psum += rounded_pair_sum<F16>(pf[j][e]);       // the denominator sums what the MFMA multiplies
-            }
-        }
-        if constexpr (!ONES) l_run += psum;
-        u32x4 vf[DT][2];                        // V^T fragments: issued together, ahead of the softmax arithmetic's tail
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const char* vrow = sV + (dt * 32 + r32) * VROW + (4 * half) * 2;
-            const int x = ((dt & 1) * 8) ^ ((dt >> 1) * 4);          // column swizzle of this 32-row tile, in key pairs (4 B)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow + ((8 * j) ^ x) * 4);
-                const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + ((8 * j + 4) ^ x) * 4);
-                vf[dt][j] = u32x4{lo[0], lo[1], hi[0], hi[1]};
-            }
-        }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                o[dt] = mfma16<F16>(vf[dt][j], pf[j], o[dt]);
-    };
-
-    commit(stg[0], 0);
-    __syncthreads();
-    const int n_main = ragged ? nkt - 1 : nkt;                   // tiles without padded keys
-    // iteration kt: tile kt is in LDS buffer kt & 1, tile kt+1 in flight / landed in register set (kt+1) & 1; set kt & 1 is
-    // free (committed at the end of iteration kt-1) and takes the loads of tile kt+2.  Unrolled by two: static set indices.
-    auto step = [&](int kt, auto par_) {
-        constexpr int PAR = decltype(par_)::value;
-        if (!(debug & 1)) fetch_any(stg[PAR], kt + 2);
-        if (!(debug & 4)) tile(kt, false_type{});
-        if (kt + 1 < nkt && !(debug & 2)) commit(stg[PAR ^ 1], (kt + 1) & 1);   // buffer last read in tile kt-1: every wave is past its barrier
-        if (!(debug & 8)) __syncthreads();
-    };
-    for (int kt = 0; kt < n_main; kt += 2) {
-        step(kt, std::integral_constant<int, 0>{});
-        if (kt + 1 < n_main) step(kt + 1, std::integral_constant<int, 1>{});
-    }
-    if (ragged) tile(nkt - 1, true_type{});
-    float l_tot;
-    if constexpr (ONES) {
-        // row dh = 88 of O^T (tile dt = 2, d_local = 24 -> reg 12 of the half-0 lanes) is sum_k P[q][k] . 1
-        static_assert(DHP == 96, "ones row: head_dim 88 in a 96-row tile");
-        l_tot = __shfl(o[2][12], r32, 64);
-    } else {
-        l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    }
-    const float inv = 1.0f / l_tot;
-    // Output through LDS: in registers a lane owns one query ROW, so storing straight out is 12 x 8 B per lane with every
-    // wave instruction touching 32 different rows -- store-issue bound, 22 us of the launch (ablation).  Each wave
-    // transposes its 32 x head_dim tile through a private strip of the (now idle) K/V buffers and writes whole rows as
-    // 16-B pieces: 5.5 instructions per lane, 176 contiguous bytes per row.
-    constexpr int ORS = DHP * 2 + 16;         // strip row stride: 16-B aligned, 2-way bank conflicts at most
-    // (the launch sizes LDS for max(K/V buffers, NW output strips))
-    __syncthreads();                          // every wave is done reading K/V tiles
-    char* so = smem + wave * (32 * ORS);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d0 = dt * 32 + 8 * g + 4 * half;
-            if (d0 < dh) {
-                uint2 pk;
-                pk.x = pack16x2<F16>(o[dt][g * 4 + 0] * inv, o[dt][g * 4 + 1] * inv);
-                pk.y = pack16x2<F16>(o[dt][g * 4 + 2] * inv, o[dt][g * 4 + 3] * inv);
-                *reinterpret_cast<uint2*>(so + r32 * ORS + d0 * 2) = pk;
-            }
-        }
-    __builtin_amdgcn_wave_barrier();          // the strip is private to this wave: LDS operations of one wave complete in order
-    const int cpr = dh >> 3;
-    char* obase = p.out + (((int64_t)b * p.Tq + qt * 32) * p.ldo + (int64_t)h * dh) * 2;
-    if (!(debug & 16)) {
-        for (int idx = lane; idx < 32 * cpr; idx += 64) {
-            const int row = idx / cpr, c = idx - row * cpr;
-            if (qt * 32 + row < p.Tq)
-#if SPRC_ATTN_NT & 1
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(so + row * ORS + c * 16), reinterpret_cast<u32x4*>(obase + (int64_t)row * p.ldo * 2 + c * 16));
-#else
-                *reinterpret_cast<u32x4*>(obase + (int64_t)row * p.ldo * 2 + c * 16) = *reinterpret_cast<const u32x4*>(so + row * ORS + c * 16);
-#endif
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Streaming kernel, second form (round 3): the K / V tiles go global -> LDS by DMA (`buffer_load_dwordx4 ... lds`) and V is
-// read back TRANSPOSED by the LDS unit (`ds_read_b64_tr_b16`).  Ablations of the first form (tools/attn_abl.sh, 135 us on the box
-// of that run): without the tile math 113 us, without loads + commit 100 us -- the staging path (two register sets of 16-B loads,
-// the commit with its eight transposing 4-B LDS writes and 16 VALU per thread and tile) weighed as much as the arithmetic.  Here
+// The K / V tiles go global -> LDS by DMA (`buffer_load_dwordx4 ... lds`) and V is read back TRANSPOSED by the LDS unit
+// (`ds_read_b64_tr_b16`).  The first streaming kernel (round 2, since removed) staged the tiles through registers into a double
+// buffer, transposing V on its way into LDS; its ablations (135 us on the box of that run): without the tile math 113 us, without
+// loads + commit 100 us -- the staging path (two register sets of 16-B loads, the commit with its eight transposing 4-B LDS writes
+// and 16 VALU per thread and tile) weighed as much as the arithmetic.  Here
 //   * a tile is 32 key rows of K (13 slots of 16 B: 208-B pitch, conflict-free for the fragments' ds_read_b128) and 32 rows of V
 //     (12 slots: 192-B pitch = 48 dwords, which spreads the four rows x two 16-column groups that a 32-lane half of a transposing
 //     read touches over all 64 banks).  A DMA instruction writes 64 consecutive slots, lane by lane, from any 64 global addresses:
 //     slot (key, chunk) <- chunk of that key's row; padding slots of K take the zeros of an out-of-range offset; slots past the K
 //     region and the V slots at d >= head_dim are masked off (EXEC) -- V's are filled once, and hold the ONES column (V[k][dh] = 1:
-//     the softmax denominator falls out of the P.V MFMAs as before);
+//     the softmax denominator falls out of the P.V MFMAs, item (2) above);
 //   * no staging registers, no commit: a ring of NBUF tiles, per key tile ONE counted `s_waitcnt vmcnt` + ONE barrier, then the
 //     DMA of tile kt + NBUF - 1 is issued into the buffer every wave has just left;
 //   * V^T fragments (A operand of O^T += V^T P^T): lane i of a 16-lane group hands the address of 8-byte piece i of a
 //     [4 keys][16 d] block (row i / 4, columns 4 (i % 4) ..) and receives column i (tools/tr_probe.hip checks this on the hardware).
-// The arithmetic of a tile (S^T = K Q^T, lazy rescale, exp2, O^T += V^T P^T) is the first form's.
+// The arithmetic of a tile is the one described above: S^T = K Q^T, lazy rescale, exp2, O^T += V^T P^T.
 template <int N>
 __device__ __forceinline__ void attn_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void attn_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, 0, 0, (SPRC_ATTN_NT & 2) ? 2 : 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, 0, 0, 0);   // (nt loads: +1.5 ms per step)
 }
 __device__ __forceinline__ u32x2 attn_tr_read(const char* lds_src) {
     typedef short v4s __attribute__((ext_vector_type(4)));
@@ -605,6 +350,10 @@ __global__ __launch_bounds__(64 * NW, NBUF == 2 ? 4 : 3) void attn_dma_kernel(At
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, half = lane >> 5;
+    // Block b runs on XCD b % 8.  A token row of the packed qkv tensor holds the K (V) slices of ALL heads back to back
+    // (176 B each for ViT-g: not a multiple of the 128-B line), so neighbouring heads share cache lines: all heads and
+    // query blocks of one image are placed on ONE XCD, consecutively, and every fetched line is used by that XCD's L2
+    // (heads spread over the XCDs fetched 457 MB per launch against 300 MB of distinct bytes).
     int b, h, qb;
     if (xcd_map == 2) { const int x = blockIdx.x & 7, i = blockIdx.x >> 3; qb = i % nqb; h = (i / nqb) % p.H; b = (i / (nqb * p.H)) * 8 + x; }
     else if (xcd_map == 1) { const int x = blockIdx.x & 7, i = blockIdx.x >> 3; qb = i % nqb; const int bh = (i / nqb) * 8 + x; b = bh / p.H; h = bh % p.H; }
@@ -683,11 +432,7 @@ __global__ __launch_bounds__(64 * NW, NBUF == 2 ? 4 : 3) void attn_dma_kernel(At
     for (int ks = 0; ks < KS; ++ks) {
         const int d0 = ks * 16 + half * 8;
         u32x4 val = {0u, 0u, 0u, 0u};
-#if SPRC_ATTN_NT & 4
-        if (d0 < dh) val = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(qptr + d0 * 2));
-#else
         if (d0 < dh) val = *reinterpret_cast<const u32x4*>(qptr + d0 * 2);
-#endif
         qf[ks] = val;
     }
 
@@ -851,6 +596,10 @@ __global__ __launch_bounds__(64 * NW, NBUF == 2 ? 4 : 3) void attn_dma_kernel(At
             return;
         }
     }
+    // Output through LDS: in registers a lane owns one query ROW, so storing straight out is 12 x 8 B per lane with every
+    // wave instruction touching 32 different rows -- store-issue bound, 22 us of the launch (ablation).  Each wave
+    // transposes its 32 x head_dim tile through a private strip of the (now idle) tile ring and writes whole rows as
+    // 16-B pieces: 5.5 instructions per lane, 176 contiguous bytes per row.
     __syncthreads();                          // every wave is done reading K/V tiles
     char* so = smem + wave * (32 * ORS);
 #pragma unroll
@@ -871,11 +620,7 @@ __global__ __launch_bounds__(64 * NW, NBUF == 2 ? 4 : 3) void attn_dma_kernel(At
         for (int idx = lane; idx < 32 * cpr; idx += 64) {
             const int row = idx / cpr, c = idx - row * cpr;
             if (qt * 32 + row < p.Tq)
-#if SPRC_ATTN_NT & 1
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(so + row * ORS + c * 16), reinterpret_cast<u32x4*>(obase + (int64_t)row * p.ldo * 2 + c * 16));
-#else
                 *reinterpret_cast<u32x4*>(obase + (int64_t)row * p.ldo * 2 + c * 16) = *reinterpret_cast<const u32x4*>(so + row * ORS + c * 16);
-#endif
         }
     };
     if (ONES) store_rows(11);                 // head_dim 88 (compile-time divisor: the run-time division cost ~25 VALU per piece)
@@ -966,37 +711,14 @@ static int launch_bf16(const AttnParams& p, hipStream_t st) {
     return SPRC_OK;
 }
 
-template <int DHP, bool ONES, int NW, bool F16>
-static int launch_stream(const AttnParams& p, hipStream_t st) {
-    constexpr int BUF = 32 * (DHP * 2 + 16) + DHP * 72;
-    constexpr int LDS = 2 * BUF > NW * 32 * (DHP * 2 + 16) ? 2 * BUF : NW * 32 * (DHP * 2 + 16);
-    const int nqb = ((p.Tq + 31) / 32 + NW - 1) / NW;
-    const int bh = p.B * p.H;
-    // SPRC_ATTN_DEBUG (timing ablations, WRONG results): 1 no global loads in the loop, 2 no LDS commit, 4 no tile math, 8 no barrier
-    static const int debug = [] { const char* e = getenv("SPRC_ATTN_DEBUG"); return e ? atoi(e) : 0; }();
-    static const int xcd = [] { const char* e = getenv("SPRC_ATTN_XCD"); return e ? atoi(e) : 1; }();
-    const int xmap = !xcd ? 0 : (xcd == 3 && (bh % 8) == 0) ? 1 : (p.B % 8) == 0 ? 2 : (bh % 8) == 0 ? 1 : 0;
-    if constexpr (!F16) {
-        if (debug != 0) {
-            hipLaunchKernelGGL((attn_stream_kernel<DHP, ONES, NW, false, true>), dim3(bh * nqb), dim3(64 * NW), LDS, st, p, nqb, xmap, debug);
-            SPRC_CHECK_LAUNCH("sprc_attention(bf16, streaming, ablation)");
-            return SPRC_OK;
-        }
-    }
-    hipLaunchKernelGGL((attn_stream_kernel<DHP, ONES, NW, F16, false>), dim3(bh * nqb), dim3(64 * NW), LDS, st, p, nqb, xmap, 0);
-    SPRC_CHECK_LAUNCH("sprc_attention(bf16, streaming)");
-    return SPRC_OK;
-}
-
 template <int DHP, bool ONES, int NW, bool F16, int NBUF>
 static int launch_dma(const AttnParams& p, hipStream_t st) {
-
     constexpr int BUF = (32 * (DHP / 8 + 1) + 63) / 64 * 1024 + 32 * 12 * 16;       // K region in whole DMA instructions + V region
     constexpr int LDS = NBUF * BUF;
     const int nqb = ((p.Tq + 31) / 32 + NW - 1) / NW;
     const int bh = p.B * p.H;
-    static const int xcd = [] { const char* e = getenv("SPRC_ATTN_XCD"); return e ? atoi(e) : 1; }();
-    const int xmap = !xcd ? 0 : (xcd == 3 && (bh % 8) == 0) ? 1 : (p.B % 8) == 0 ? 2 : (bh % 8) == 0 ? 1 : 0;
+    // XCD map (attn_dma_kernel): whole images per XCD when B % 8 == 0, else (image, head) pairs when B H % 8 == 0, else none
+    const int xmap = (p.B % 8) == 0 ? 2 : (bh % 8) == 0 ? 1 : 0;
     hipLaunchKernelGGL((attn_dma_kernel<DHP, ONES, NW, F16, NBUF>), dim3(bh * nqb), dim3(64 * NW), LDS, st, p, nqb, xmap);
     SPRC_CHECK_LAUNCH("sprc_attention(16-bit, streaming, DMA)");
     return SPRC_OK;
@@ -1017,43 +739,23 @@ static int attention16(const sprc_attention_args* a, const AttnParams& p, bool t
     SPRC_REQUIRE(!two || (a->ldk2 % 8 == 0 && a->ldv2 % 8 == 0 && ((uintptr_t)a->k2 % 16) == 0 && ((uintptr_t)a->v2 % 16) == 0),
                  "sprc_attention(16-bit): second key segment misaligned");
     const bool small = a->Tq <= 128;
-    // long query axes without a key mask (the ViT blocks): streaming kernel, four workgroups of three waves per CU (153 VGPRs;
-    // 5- and 9-wave workgroups measured 268 / 170 us against 125: fewer co-resident workgroups).
-    // (SPRC_ATTN_STREAM=0 keeps the resident-K/V kernel for A/B runs)
-    static const int stream = [] { const char* e = getenv("SPRC_ATTN_STREAM"); return e ? atoi(e) : 1; }();
-    // SPRC_ATTN_DMA: 0 = the first streaming form (register staging), 2 / 3 = the DMA form with a ring of that many tiles
-    static const int dma = [] { const char* e = getenv("SPRC_ATTN_DMA"); return e ? atoi(e) : 2; }();
     // ONE 32-query tile over a long key axis (the Q-Former's cross-attention: 32 query tokens x 257 encoder tokens, 12 heads x 64; Qformer.py:175-281):
     // the resident kernel stages all of K and V^T through registers into LDS with four waves and then multiplies on ONE of them (108.9 us per
-    // launch of 233 x 12 heads against a ~37-us memory floor).  The streaming DMA kernel with ONE-wave workgroups keeps a ring of 32-key tiles
-    // per workgroup (11.3 KB each), 7 / 4 workgroups per CU (ring of 2 / 3).  SPRC_ATTN_CROSS: 0 = the resident kernel (A/B), 2 (default) / 3 = ring depth.
-    // Measured (profiles/r06_cross_attn_ab.txt; launches alone, K|V rows of 9216 elements as in the model): 233 x 12 heads 88.3 -> 39.1 us (ring of 2;
-    // 45.5 with a ring of 3: fewer workgroups per CU), 128 x 12 heads 47.5 -> 21.3; the bench step 88.0 -> 87.65 ms, same box, alternating.
-    static const int cross = [] { const char* e = getenv("SPRC_ATTN_CROSS"); return e ? atoi(e) : 2; }();
+    // launch of 233 x 12 heads against a ~37-us memory floor).  The streaming DMA kernel with ONE-wave workgroups keeps a ring of two 32-key tiles
+    // per workgroup (11.3 KB each), 7 workgroups per CU.  Measured (profiles/r06_cross_attn_ab.txt; launches alone, K|V rows of 9216 elements as in
+    // the model): 233 x 12 heads 88.3 -> 39.1 us (45.5 with a ring of three: fewer workgroups per CU), 128 x 12 heads 47.5 -> 21.3; the bench step
+    // 88.0 -> 87.65 ms, same box, alternating.
     // (kv_index on ONE segment -- sprc_qformer_fuse_kv -- takes the same kernel: its scores stay bit-identical to the per-query projection's)
-    if (cross && a->Tq <= 32 && p.Tk >= 128 && a->head_dim <= 64 && a->key_mask == nullptr && !two &&
+    if (a->Tq <= 32 && p.Tk >= 128 && a->head_dim <= 64 && a->key_mask == nullptr && !two &&
         (a->out_x3 ? F16 : (a->ldo % 8 == 0 && ((uintptr_t)a->out % 16) == 0))) {
-        return cross == 2 ? launch_dma<64, false, 1, F16, 2>(p, st) : launch_dma<64, false, 1, F16, 3>(p, st);
+        return launch_dma<64, false, 1, F16, 2>(p, st);
     }
-    if (stream && dma && !small && a->key_mask == nullptr && !two && a->kv_index == nullptr && a->ldo % 8 == 0 && ((uintptr_t)a->out % 16) == 0) {
-        static const int nw4 = [] { const char* e = getenv("SPRC_ATTN_NW"); return e ? atoi(e) == 4 : 0; }();
-        if (dma == 2 && nw4) {
-            if (a->head_dim <= 64) return launch_dma<64, false, 4, F16, 2>(p, st);
-            if (a->head_dim == 88) return launch_dma<96, true, 4, F16, 2>(p, st);
-        }
-        if (dma == 2) {
-            if (a->head_dim <= 64) return launch_dma<64, false, 3, F16, 2>(p, st);
-            if (a->head_dim == 88) return launch_dma<96, true, 3, F16, 2>(p, st);
-            return launch_dma<96, false, 3, F16, 2>(p, st);
-        }
-        if (a->head_dim <= 64) return launch_dma<64, false, 3, F16, 3>(p, st);
-        if (a->head_dim == 88) return launch_dma<96, true, 3, F16, 3>(p, st);
-        return launch_dma<96, false, 3, F16, 3>(p, st);
-    }
-    if (stream && !small && a->key_mask == nullptr && !two && a->kv_index == nullptr && a->ldo % 8 == 0 && ((uintptr_t)a->out % 16) == 0) {
-        if (a->head_dim <= 64) return launch_stream<64, false, 3, F16>(p, st);
-        if (a->head_dim == 88) return launch_stream<96, true, 3, F16>(p, st);     // denominator from the ones row of the padded V^T tile
-        return launch_stream<96, false, 3, F16>(p, st);
+    // long query axes without a key mask (the ViT blocks): streaming kernel, four workgroups of three waves per CU (153 VGPRs;
+    // 5- and 9-wave workgroups measured 268 / 170 us against 125: fewer co-resident workgroups), a ring of two tiles
+    if (!small && a->key_mask == nullptr && !two && a->kv_index == nullptr && a->ldo % 8 == 0 && ((uintptr_t)a->out % 16) == 0) {
+        if (a->head_dim <= 64) return launch_dma<64, false, 3, F16, 2>(p, st);
+        if (a->head_dim == 88) return launch_dma<96, true, 3, F16, 2>(p, st);     // denominator from the ones row of the padded V^T tile
+        return launch_dma<96, false, 3, F16, 2>(p, st);
     }
     // 257 tokens = 9 query tiles: nine waves (one tile each, the K / V staging shared by nine) beat eight waves of which
     // one carries two tiles: 209 -> 195 us per ViT-g layer
@@ -1062,13 +764,11 @@ static int attention16(const sprc_attention_args* a, const AttnParams& p, bool t
         if (a->head_dim <= 64) return launch_bf16<64, 9, F16>(p, st);
         return launch_bf16<96, 9, F16>(p, st);
     }
-    // small query axes (the Q-Former: 32 or 64 query rows = one or two 32-row tiles): SPRC_ATTN_SMALL_NW waves per workgroup
-    static const int small_nw = [] { const char* e = getenv("SPRC_ATTN_SMALL_NW"); return e ? atoi(e) : 4; }();
+    // small query axes (the Q-Former: 32 or 64 query rows = one or two 32-row tiles)
     // measured (tools/qf_attn_bench.py, 233 x 12 heads): self-attention over 64 keys 40.9 us with four waves per workgroup, 28.5 with
     // two (one per query tile: twice the workgroups per CU); cross-attention over 257 keys 84.5 / 106.8 / 142.5 us with 4 / 2 / 1
     // waves (there the extra waves carry the K / V staging) -> two waves for short key axes, four otherwise
-    if (a->head_dim <= 64 && small && (small_nw == 2 || (small_nw == 4 && Tk_all_le64(p)))) return launch_bf16<64, 2, F16>(p, st);
-    if (a->head_dim <= 64 && small && small_nw == 1) return launch_bf16<64, 1, F16>(p, st);
+    if (a->head_dim <= 64 && small && Tk_all_le64(p)) return launch_bf16<64, 2, F16>(p, st);
     if (a->head_dim <= 64) return small ? launch_bf16<64, 4, F16>(p, st) : launch_bf16<64, 8, F16>(p, st);
     return small ? launch_bf16<96, 4, F16>(p, st) : launch_bf16<96, 8, F16>(p, st);
 }
@@ -1082,7 +782,8 @@ extern "C" int sprc_attention(const sprc_attention_args* a, sprc_stream s) {
     SPRC_REQUIRE(!two || (a->v2 && a->Tk2 > 0 && !a->key_mask), "sprc_attention: a second key segment needs k2, v2, Tk2 > 0 and no key mask");
     SPRC_REQUIRE(two || (!a->kv2_index && !a->v2), "sprc_attention: kv2_index / v2 come with a second key segment (k2)");
     SPRC_REQUIRE(!a->kv_index || two || a->Tq <= 128 || a->dtype == SPRC_F32,
-                 "sprc_attention: kv_index on a single key segment is served by the resident kernels (Tq <= 128) and the fp32 one");
+                 "sprc_attention: kv_index on a single key segment is served by the kernels for Tq <= 128 (the resident ones and the one-wave "
+                 "streaming cross-attention kernel) and the fp32 one");
     const int Tk_all = a->Tk + (two ? a->Tk2 : 0);
     AttnParams p{a->B, a->H, a->Tq, Tk_all, a->head_dim, (const char*)a->q, a->ldq, (const char*)a->k, a->ldk,
                  (const char*)a->v, a->ldv, (char*)a->out, a->ldo, a->key_mask, a->scale,

@@ -1,6 +1,5 @@
 // core.hip -- version, error reporting, CU-partition streams, the per-launch profiler
 #include <stdarg.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <mutex>
@@ -123,11 +122,8 @@ extern "C" int sprc_stream_create_partition(int32_t part, int32_t nparts, sprc_s
     // partition `part` takes the CUs whose index inside their XCD is congruent to it -- the same share of every XCD and of every XCD's L2
     uint32_t mask[32] = {0};
     int n = 0;
-    const char* le = getenv("SPRC_PART_LAYOUT");     // probe switch (tools/cumask_probe.py): 0 = per-XCD shares (default), 1 = whole XCDs
-    const int layout = le ? atoi(le) : 0;            // (bit i % 8), 2 = alternate bits, 3 = contiguous bit ranges
     for (int i = 0; i < ncu; ++i) {
-        const int owner = layout == 1 ? (i % 8) * nparts / 8 : layout == 2 ? i % nparts : layout == 3 ? (int)((int64_t)i * nparts / ncu) : (i / 8) % nparts;
-        if (owner == part) { mask[i >> 5] |= 1u << (i & 31); ++n; }
+        if ((i / 8) % nparts == part) { mask[i >> 5] |= 1u << (i & 31); ++n; }
     }
     hipStream_t st = nullptr;
     const hipError_t e = hipExtStreamCreateWithCUMask(&st, (uint32_t)((ncu + 31) / 32), mask);

@@ -70,12 +70,9 @@ static int gemm_impl(const sprc_gemm_args* a, const sprc_gemm_args* b, sprc_stre
     }
     p.scratch = reinterpret_cast<float*>(a->scratch); p.scratch_elems = (int64_t)(a->scratch_bytes / 4);
     p.w_scale = a->dtype == SPRC_FP8 ? a->w_scale : nullptr; p.a_scale = a->a_scale; p.out_scale = a->out_scale;
-    static const int dbg = env_int("SPRC_GEMM_DEBUG", 0) | (env_int("SPRC_GEMM_DEAD", 1) ? 0 : 128);     // bit 128: dead waves multiply like live ones (A/B)
+    static const int dbg = env_int("SPRC_GEMM_DEBUG", 0);
     p.debug = dbg;
-    p.duo_sleep = 0; p.duo_ctr = nullptr;
-    static const int epi_wide = env_int("SPRC_EPI_WIDE", 1);       // 0: 4 columns per lane in every epilogue (A/B switch, gemm_epilogue)
-    p.epi_wide = epi_wide;
-    p.order = -1;                       // per-kernel default (launch_*), SPRC_GEMM_ORDER overrides
+    p.order = -1;                       // per-kernel default (launch_*)
     p.k8 = a->k8;
     hipStream_t st = (hipStream_t)s;
     const double osz = a->max32 ? 4.0 / 32.0 : a->out_dtype == SPRC_F16X3 ? 4.0 : (double)dtype_size(a->out_dtype);     // a split row: 4 bytes per column

@@ -58,9 +58,6 @@ struct GemmParams {
     int debug;                          // SPRC_GEMM_DEBUG on the 256x256 kernel: 64 s_memtime stamp build (tools/gemm_stamp.py)
     int k8;                             // MIX kernels (split-precision products): e4m3 reduction elements that FOLLOW the K fp16 elements in
                                         // every row of A and W (K-tiles of 128 bytes either way); their partial sum enters scaled by 2^-18
-    int duo_sleep;                      // duo kernel (gemm_duo.hpp): cycles the second workgroup of a CU sleeps before its first tile (0: no stagger)
-    int* duo_ctr;                       // duo kernel: per-CU arrival counters (DUO_CTRS ints, only ever incremented)
-    int epi_wide;                       // 1: 8 columns per lane in the epilogues of outputs narrower than fp32 (16-B stores); 0: 4 (A/B switch)
 };
 
 // MX block scales of the split-precision products' e4m3 segments: E8M0 118 = 2^-9 on BOTH operands -> 2^-18 on the product, the
@@ -95,25 +92,18 @@ __device__ __forceinline__ uint32_t pack_fp8x2(float a, float b, uint32_t old, b
     b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
     return hi ? (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, (int)old, true) : (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, (int)old, false);
 }
-// Cache policy of the epilogue's global accesses (bit mask; -DSPRC_EPI_NT=0 is the A/B build without any hint).  1: the 16-byte stores of outputs
-// narrower than fp32 are NON-TEMPORAL (`global_store_dwordx4 ... nt`): at the end of a round 256 workgroups write 33 MB of qkv / fc1 output at
-// once -- more than the L2s hold -- and with the default write-allocate policy that burst evicts the A / W panels every CU re-reads in the next
-// round.  Same box, round-robin (profiles/r06_nt_ab.txt): 87.61 -> 86.76 ms per bench step, GEMM class 78.2 -> 77.2 ms.  2: fp32 stores as well
-// (86.72: neutral -- the LayerNorm reads x right behind them), 4: non-temporal residual loads (neutral).  NT on the staging LOADS of either operand costs
-// 3-4 ms (SPRC_LD_NT), NT attention loads 1.5 ms, NT stores of the attention output or of the LayerNorm's 16-bit copy 0.2-0.3 ms: those are re-read.
-#ifndef SPRC_EPI_NT
-#define SPRC_EPI_NT 1
-#endif
+// Cache policy of the epilogue's global accesses: the 16-byte stores of outputs narrower than fp32 are NON-TEMPORAL
+// (`global_store_dwordx4 ... nt`): at the end of a round 256 workgroups write 33 MB of qkv / fc1 output at once -- more than the L2s hold --
+// and with the default write-allocate policy that burst evicts the A / W panels every CU re-reads in the next round.  Same box, round-robin
+// (profiles/r06_nt_ab.txt): 87.61 -> 86.76 ms per bench step, GEMM class 78.2 -> 77.2 ms against no hint.  Measured and not adopted: fp32 stores
+// as well (86.72: neutral -- the LayerNorm reads x right behind them), non-temporal residual loads (neutral).  NT on the staging LOADS of either
+// operand costs 3-4 ms, NT attention loads 1.5 ms, NT stores of the attention output or of the LayerNorm's 16-bit copy 0.2-0.3 ms: those are re-read.
 // 4 consecutive outputs of one row: 16 B (fp32) or 8 B (bf16 / fp16)
 // n_split / col: logical row width N and this quad's first column (SPRC_F16X3 outputs only: the e4m3 segments sit behind the N fp16 values)
 template <typename OutT>
 __device__ __forceinline__ void store_out4(OutT* dst, const f32x4& v, int n_split = 0, int col = 0) {
     if constexpr (std::is_same<OutT, float>::value) {
-#if SPRC_EPI_NT & 2
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
-#else
         *reinterpret_cast<f32x4*>(dst) = v;
-#endif
     } else if constexpr (std::is_same<OutT, f16x3_t>::value) {
         store_split4(reinterpret_cast<char*>(dst) - 2 * col, n_split, col, v[0], v[1], v[2], v[3]);
     } else if constexpr (std::is_same<OutT, f16_t>::value) {
@@ -133,26 +123,13 @@ __device__ __forceinline__ void store_out8(OutT* dst, const f32x4& a, const f32x
     if constexpr (std::is_same<OutT, f16x3_t>::value) {
         store_split8(reinterpret_cast<char*>(dst) - 2 * col, n_split, col, a, b);
     } else if constexpr (std::is_same<OutT, f16_t>::value) {
-#if SPRC_EPI_NT & 1
         __builtin_nontemporal_store(u32x4{pack_f16x2(a[0], a[1]), pack_f16x2(a[2], a[3]), pack_f16x2(b[0], b[1]), pack_f16x2(b[2], b[3])}, reinterpret_cast<u32x4*>(dst));
-#else
-        *reinterpret_cast<u32x4*>(dst) = u32x4{pack_f16x2(a[0], a[1]), pack_f16x2(a[2], a[3]), pack_f16x2(b[0], b[1]), pack_f16x2(b[2], b[3])};
-#endif
     } else if constexpr (std::is_same<OutT, fp8_t>::value) {
-#if SPRC_EPI_NT & 1
         __builtin_nontemporal_store(u32x2{pack_fp8x2(a[2], a[3], pack_fp8x2(a[0], a[1], 0u, false), true),
                                           pack_fp8x2(b[2], b[3], pack_fp8x2(b[0], b[1], 0u, false), true)}, reinterpret_cast<u32x2*>(dst));
-#else
-        *reinterpret_cast<u32x2*>(dst) = u32x2{pack_fp8x2(a[2], a[3], pack_fp8x2(a[0], a[1], 0u, false), true),
-                                               pack_fp8x2(b[2], b[3], pack_fp8x2(b[0], b[1], 0u, false), true)};
-#endif
     } else {
         static_assert(std::is_same<OutT, bf16_t>::value, "store_out8: outputs narrower than fp32");
-#if SPRC_EPI_NT & 1
         __builtin_nontemporal_store(u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])}, reinterpret_cast<u32x4*>(dst));
-#else
-        *reinterpret_cast<u32x4*>(dst) = u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
-#endif
     }
 }
 
@@ -178,12 +155,8 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const char* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, 0xffffffff, 0x00020000);
 }
-#ifndef SPRC_LD_NT
-#define SPRC_LD_NT 0
-#endif
-template <int AUX = 0>
 __device__ __forceinline__ void buffer_load_lds16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds_dst, 16, voffset, soffset, 0, AUX);     // AUX 2 = nt (gfx940+ cache policy bits: 1 sc0, 2 nt, 16 sc1)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds_dst, 16, voffset, soffset, 0, 0);     // default cache policy (nt: +3-4 ms per step)
 }
 
 template <int I, int N, typename F>
@@ -214,18 +187,12 @@ __device__ __forceinline__ void wait_lgkmcnt() {
 // One K-tile (4 MFMA k-steps) of a wave's TM x TN accumulator block, hand software-pipelined.
 // a_base / b_base: LDS byte address of this lane's first A / W row in the current stage; c0 = swizzled slot of
 // k-step 0 ((half ^ f(row)) << 4); k-step kk reads slot c0 ^ (kk << 5).
-// fp8 (FP8 = true): a 16-B fragment holds 16 k-values = TWO e4m3 MFMA k-steps (low / high 8 bytes); which bytes form a
-// k-step is a free permutation of k as long as both operands use the same one, so the LDS layout and the reads are the bf16 ones.
-// T = operand type of the 16-B fragments: bf16_t, f16_t (v_mfma_f32_32x32x16_f16: same rate, same fragment layout, 11-bit
-// significands -- the reference's own GPU precision, blip2.py:36-44) or fp8_t.
+// T = operand type of the 16-B fragments: bf16_t or f16_t (v_mfma_f32_32x32x16_f16: same rate, same fragment layout, 11-bit
+// significands -- the reference's own GPU precision, blip2.py:36-44).  fp8 K-tiles run on the MX-scaled MFMA (mfma_mx / mfma_mx8).
 template <typename T>
 __device__ __forceinline__ f32x16 mfma_frag(const u32x4& b, const u32x4& a, f32x16 c) {
-    if constexpr (std::is_same<T, fp8_t>::value) {
-        const long b0 = (long)(((uint64_t)b[1] << 32) | b[0]), b1 = (long)(((uint64_t)b[3] << 32) | b[2]);
-        const long a0 = (long)(((uint64_t)a[1] << 32) | a[0]), a1 = (long)(((uint64_t)a[3] << 32) | a[2]);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(b0, a0, c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(b1, a1, c, 0, 0, 0);
-    } else if constexpr (std::is_same<T, f16_t>::value) {
+    static_assert(sizeof(T) == 2, "16-bit operands");
+    if constexpr (std::is_same<T, f16_t>::value) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, b), __builtin_bit_cast(f16x8, a), c, 0, 0, 0);
     } else {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
@@ -235,31 +202,12 @@ __device__ __forceinline__ f32x16 mfma_frag(const u32x4& b, const u32x4& a, f32x
 // MX-scaled e4m3 MFMA with unit block scales (E8M0 127 = 2^0): v_mfma_scale_f32_32x32x64_f8f6f4 covers K = 64 per instruction
 // at TWICE the rate of the non-scaled fp8 / bf16 instructions (5 PF dense).  A lane supplies 32 bytes = two 16-B fragments
 // of the bf16 LDS layout; with all scales 1 the k-order inside the 64 is a free permutation shared by both operands.
-// SPRC_FP8_MX 0 falls back to two non-scaled 32x32x16 steps per fragment (bf16 rate).
-#ifndef SPRC_ANTI_LDPOS
-#define SPRC_ANTI_LDPOS 1          // the in-cluster load goes out after MFMA number LDPOS (0..15)
-#endif
-#ifndef SPRC_FP8_MX
-#define SPRC_FP8_MX 1
-#endif
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 // volatile asm: as a pure intrinsic hipcc SINKS the MFMAs of a whole K-tile pair to the loop latch (legal, and fatal for the
 // interval structure); the statement stays where it is written.  Callers keep >= 8 other MFMAs between two uses of one
 // accumulator (no hazard nops are inserted for inline asm).
-// SPRC_MX_FP6_TIMING (variant builds only, tools/r06_ab_fp6.sh; WRONG results): the correction segments' MFMAs issued in the fp6 (e2m3) format on
-// the first 24 of the 32 operand bytes -- half the passes of the e4m3 form -- to MEASURE what fp6 correction segments would buy before any
-// producer writes them.
-#ifndef SPRC_MX_FP6_TIMING
-#define SPRC_MX_FP6_TIMING 0
-#endif
 __device__ __forceinline__ f32x16 mfma_mx8(const i32x8& bb, const i32x8& aa, f32x16 c, int sc = MX_UNIT_SCALE) {
     // sc: the E8M0 block scale of BOTH operands in every byte (0x7f = 2^0: unit scales; MX_SPLIT_SCALE for the split-precision segments)
-    if constexpr (SPRC_MX_FP6_TIMING != 0) {
-        typedef __attribute__((ext_vector_type(6))) int i32x6;
-        const i32x6 b6 = {bb[0], bb[1], bb[2], bb[3], bb[4], bb[5]}, a6 = {aa[0], aa[1], aa[2], aa[3], aa[4], aa[5]};
-        asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0] cbsz:2 blgp:2" : "+v"(c) : "v"(b6), "v"(a6), "v"(sc));
-        return c;
-    }
     asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(bb), "v"(aa), "v"(sc));
     return c;
 }
@@ -275,8 +223,7 @@ template <int SC = MX_UNIT_SCALE>
 __device__ __forceinline__ f32x16 mfma_mx(const u32x4& b0, const u32x4& b1, const u32x4& a0, const u32x4& a1, f32x16 c) {
     const i32x8 bb = {(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], (int)b1[2], (int)b1[3]};
     const i32x8 aa = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
-    constexpr int FMT = SPRC_MX_FP6_TIMING != 0 ? 2 /* e2m3: timing variant, see mfma_mx8 */ : 0 /* e4m3 */;
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bb, aa, c, FMT, FMT, 0, SC, 0, SC);
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bb, aa, c, 0, 0, 0, SC, 0, SC);     // formats 0: e4m3
 }
 
 // One K-tile of the 128x128 kernel on MX fp8: two K = 64 steps, each from a PAIR of 16-B fragments per operand row-tile; the
@@ -351,7 +298,7 @@ __device__ __forceinline__ void tile_origin(int vb, int nwg, int tiles_m, int ti
     const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
     const int pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
     if ((mode & 255) == 0) {
-        const int GROUP_M = (mode >> 8) ? (mode >> 8) : 4;     // SPRC_GEMM_ORDER = 0 | GROUP_M << 8 forces another group height (A/B)
+        const int GROUP_M = (mode >> 8) ? (mode >> 8) : 4;     // mode 0 | GROUP_M << 8: another group height (launch_cfg: 8)
         const int in_group = GROUP_M * tiles_n;
         const int first_m = (pid / in_group) * GROUP_M;
         const int gsz = min(tiles_m - first_m, GROUP_M);
@@ -408,7 +355,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
             // W = columns per lane.  4: one 16-B strip read, 16-B (fp32) / 8-B (16-bit) / 4-B (fp8) stores.  8 (outputs narrower than
             // fp32, N % 8 == 0): two strip reads, ONE 16-B store per lane for 16-bit outputs -- the store tail of a 16-bit epilogue is
             // store-ISSUE-bound (guide T21: half the instructions at equal bytes halve it), and a wave instruction then covers 8 rows x
-            // 128 B = whole cache lines.  SPRC_EPI_WIDE=0 keeps W = 4 (A/B switch).
+            // 128 B = whole cache lines.
             auto vec_path = [&](auto w_) {
             constexpr int W = decltype(w_)::value, NV = W / 4;
             constexpr int CH = 32 * TN / W, RPI = 64 / CH, ITERS = 32 / RPI, LD = (32 * TN + 4) * 4;   // chunks per row, rows per instruction
@@ -464,11 +411,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
                     for (int it = 0; it < ITERS; ++it) {
                         const uint32_t ro = __umul24((uint32_t)(mrow(min(block_row(mi, it), p.M - 1)) - row0m), ldr32) + (uint32_t)colc;
 #pragma unroll
-#if SPRC_EPI_NT & 4
-                        for (int j = 0; j < NV; ++j) dst[it][j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(rbase + ro + 4 * j));
-#else
                         for (int j = 0; j < NV; ++j) dst[it][j] = *reinterpret_cast<const f32x4*>(rbase + ro + 4 * j);
-#endif
                     }
                 };
                 if constexpr (RES) {
@@ -517,7 +460,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
             else body(std::false_type{});
             };
             if constexpr (sizeof(OutT) < 4) {
-                const bool wide_ok = p.epi_wide && (p.N % 8 == 0) && (p.ldc % 8 == 0) && ((uintptr_t)p.C % 16 == 0);
+                const bool wide_ok = (p.N % 8 == 0) && (p.ldc % 8 == 0) && ((uintptr_t)p.C % 16 == 0);
                 if (wide_ok) { vec_path(std::integral_constant<int, 8>{}); return; }
             }
             vec_path(std::integral_constant<int, 4>{});
@@ -685,7 +628,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(GemmParams p) {
                     constexpr int kk = decltype(kk_)::value;
                     if (more) static_for<kk * LQ, (kk + 1) * LQ>([&](auto j_) { stage_one(j_, dst, ko); });
                 };
-                if constexpr (sizeof(T) == 1 && SPRC_FP8_MX) pipe_ktile_mx<TM, TN, KT_BYTES>(so + a_off, so + b_off, c0, acc, issue);
+                if constexpr (sizeof(T) == 1) pipe_ktile_mx<TM, TN, KT_BYTES>(so + a_off, so + b_off, c0, acc, issue);
                 else if constexpr (MIX) {
                     if (t < nt16) pipe_ktile_bf16<TM, TN, KT_BYTES, T>(so + a_off, so + b_off, c0, acc, issue);
                     else pipe_ktile_mx<TM, TN, KT_BYTES, MX_SPLIT_SCALE>(so + a_off, so + b_off, c0, acc, issue);
@@ -790,12 +733,12 @@ template <typename T, typename OutT, int ACT, bool MAX32, bool STAMP = false, bo
 __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(sizeof(T) <= 2, "16-bit or fp8 operands");
-    static_assert(!MIX || (std::is_same<T, f16_t>::value && SPRC_FP8_MX), "MIX: fp16 main segment + MX e4m3 segments");
+    static_assert(!MIX || std::is_same<T, f16_t>::value, "MIX: fp16 main segment + MX e4m3 segments");
     constexpr bool FP8 = sizeof(T) == 1;
     constexpr int WN = 4, TM = 4, TN = 2, KTB = 128;
     constexpr int BM = 256, BN = 256;
-    // PERSISTENT tile loop: workgroup b takes tiles b, b + gridDim, ... (the launcher sizes the grid: one workgroup per tile, or -- SPRC_GEMM_PERSIST
-    // -- one per CU; gridDim is a multiple of 8 there, so a workgroup's tiles keep its XCD).  Nothing but the tile index lives across an
+    // PERSISTENT tile loop: workgroup b takes tiles b, b + gridDim, ... (the launcher sizes the grid: one workgroup per tile, or one per CU
+    // when there are more tiles than CUs; gridDim is a multiple of 8 there, so a workgroup's tiles keep its XCD).  Nothing but the tile index lives across an
     // iteration: every tile re-derives its state from the (laundered) kernarg pointer and a laundered thread index, so that no
     // loop-invariant register survives the epilogue.
     int total_tiles;
@@ -831,10 +774,10 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     // quarters 2 and 3, a twelfth of those launches' matrix work; qkv's 17th column likewise) multiplies clamped copies of row N - 1 into
     // accumulators nobody stores.  The step is POWER-bound (a product alone on half the chip runs 1.25 x the clock: profiles/r06_cumask_probe.txt),
     // so what those MFMAs and fragment reads cost is clock for everybody else.  A dead wave keeps its share of the staging loads, the counted
-    // waits and every barrier -- the interval skeleton below, without reads and clusters -- and skips the epilogue.  SPRC_GEMM_DEAD=0 (debug
-    // bit 128): A/B switch; same box, alternating: 87.5 / 87.9 / 88.1 ms per step with, 88.4 / 88.6 / 88.5 without (profiles/r06_dead_waves_ab.txt).
+    // waits and every barrier -- the interval skeleton below, without reads and clusters -- and skips the epilogue.  Measured against dead waves
+    // that multiply like live ones, same box, alternating: 87.5 / 87.9 / 88.1 ms per step with, 88.4 / 88.6 / 88.5 without (profiles/r06_dead_waves_ab.txt).
     // (the same for a wave whose 128 ROWS lie at or beyond M: the lower half of a ragged last row panel)
-    const bool dead = !(kq->debug & 128) && (__builtin_amdgcn_readfirstlane(n0 + wc * (TN * 32)) >= kq->N || m0 + wr * (TM * 32) >= kq->M);
+    const bool dead = __builtin_amdgcn_readfirstlane(n0 + wc * (TN * 32)) >= kq->N || m0 + wr * (TM * 32) >= kq->M;
     f32x16 acc[TM][TN];
     auto zero_acc = [&]() {
 #pragma unroll
@@ -903,8 +846,7 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
         addr_a[x] = lds0 + (wr * TM * 32 + r32) * KTB + (c0 ^ (uint32_t)(x << 5));
         addr_b[x] = lds0 + B_BASE + (wc * TN * 32 + r32) * KTB + (c0 ^ (uint32_t)(x << 5));
     }
-    constexpr bool MX = FP8 && SPRC_FP8_MX;
-    typedef std::integral_constant<bool, MIX || MX> MXL;    // element kind of a K-tile: MXL for every tile of a plain kernel; MIX kernels
+    typedef std::integral_constant<bool, MIX || FP8> MXL;    // element kind of a K-tile: MXL for every tile of a plain kernel; MIX kernels
                                                             // pass false_type for their fp16 tiles and MXL (= true) for the e4m3 ones
     constexpr int MXSC = MIX ? MX_SPLIT_SCALE : MX_UNIT_SCALE;
     u32x4 fa[2][TM], fb[2][TN];
@@ -927,9 +869,7 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     // load j (of 2) of piece q (G0: B0 B1 | A2 A3, G1: B2 B3 | A0 A1) of K-tile `tile` into the stage of parity par_bytes / 32 KB
     auto load_piece = [&](auto q_, auto j_, uint32_t par_bytes, int tile) {
         constexpr int q = decltype(q_)::value, j = decltype(j_)::value;
-        // SPRC_LD_NT (A/B builds only): bit 0 / 1 = nt on the A / W loads (measured: +3-4 ms per step), bit 2 / 3 = sc0 on them
-        if constexpr (q >= 2) buffer_load_lds16<((SPRC_LD_NT & 1) ? 2 : 0) | ((SPRC_LD_NT & 4) ? 1 : 0)>(rs_a, smem + (base_q[q] + par_bytes + j * 4096), pc_off[q][j], tile * KTB);
-        else buffer_load_lds16<((SPRC_LD_NT & 2) ? 2 : 0) | ((SPRC_LD_NT & 8) ? 1 : 0)>(rs_w, smem + (base_q[q] + par_bytes + j * 4096), pc_off[q][j], tile * KTB);
+        buffer_load_lds16(q >= 2 ? rs_a : rs_w, smem + (base_q[q] + par_bytes + j * 4096), pc_off[q][j], tile * KTB);
     };
     auto piece = [&](auto q_, uint32_t par_bytes, int tile) { load_piece(q_, I0{}, par_bytes, tile); load_piece(q_, I1{}, par_bytes, tile); };
     // fragments of k-steps 2h, 2h+1 of the K-tile in the stage of parity PAR: compile-time parity = pure immediates
@@ -972,21 +912,21 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
             static_for<0, TN>([&](auto i) { fb[k][i] = lds_read128<decltype(i)::value * 32 * KTB>(bn); });
         });
     };
-    // 16 MFMAs (k-steps 2h, 2h+1 of the 128 x 64 wave tile); the second load of piece q goes out after MFMA number
-    // SPRC_ANTI_LDPOS (`ld`: a compile-time true in the steady state, a run-time flag in the last K-tiles)
+    // 16 MFMAs (k-steps 2h, 2h+1 of the 128 x 64 wave tile; 8 on MX K-tiles); the second load of piece q goes out after MFMA 1
+    // (MX: MFMA 0, the same point in the cluster) (`ld`: a compile-time true in the steady state, a run-time flag in the last K-tiles)
     auto cluster = [&](auto q_, uint32_t par_bytes, auto ld, int tile, auto mx_) {
         __builtin_amdgcn_s_setprio(1);
         if constexpr (decltype(mx_)::value) {
             static_for<0, 8>([&](auto x_) {
                 constexpr int x = decltype(x_)::value, mi = x >> 1, ni = x & 1;
                 acc[mi][ni] = mfma_mx8(fb8[ni], fa8[mi], acc[mi][ni], MXSC);
-                if constexpr (x == (SPRC_ANTI_LDPOS) / 2) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
+                if constexpr (x == 0) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
             });
         } else {
             static_for<0, 16>([&](auto x_) {
                 constexpr int x = decltype(x_)::value, k = x >> 3, mi = (x >> 1) & 3, ni = x & 1;
                 acc[mi][ni] = mfma_frag<T>(fb[k][ni], fa[k][mi], acc[mi][ni]);
-                if constexpr (x == (SPRC_ANTI_LDPOS)) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
+                if constexpr (x == 1) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
             });
         }
         __builtin_amdgcn_s_setprio(0);
@@ -1193,24 +1133,6 @@ static void optin_lds(K kern, int bytes, bool (&done)[MAX_DEVICES]) {
     }
 }
 
-// one helper stream + fork / join events per device (streams and events belong to the device they were created on)
-struct SideStream { hipStream_t st; hipEvent_t fork, join; };
-static SideStream* side_stream() {
-    static const int on = env_int("SPRC_GEMM_SIDE", 0);      // off: measured 89.7 -> 93.0 ms per bench step WITH it (see the call site)
-    if (!on) return nullptr;
-    static SideStream pool[MAX_DEVICES] = {};
-    static int state[MAX_DEVICES] = {0};                // 0 = not created yet, 1 = ready, -1 = creation failed
-    const int dev = current_device();
-    if (state[dev] == 0) {
-        SideStream& h = pool[dev];
-        const bool ok = hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking) == hipSuccess &&
-                        hipEventCreateWithFlags(&h.fork, hipEventDisableTiming) == hipSuccess &&
-                        hipEventCreateWithFlags(&h.join, hipEventDisableTiming) == hipSuccess;
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1 ? &pool[dev] : nullptr;
-}
-
 template <typename T, typename OutT, int ACT, bool MAX32, int WM, int WN, int TM, int TN, int RESIDENT, int NS = 2, bool MIX = false>
 static int launch_cfg(GemmParams p, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, LDS = NS * (BM + BN) * 128;
@@ -1222,8 +1144,7 @@ static int launch_cfg(GemmParams p, hipStream_t st) {
     optin_lds(kern, LDS, attr_set);
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
-    static const int order = env_int("SPRC_GEMM_ORDER", 8 << 8);     // 8-m grouped order (mode 0, GROUP_M 8) is better for the K-heavy 128x128 GEMMs
-    p.order = order;
+    p.order = 8 << 8;                   // 8-m grouped order (mode 0, GROUP_M 8) is better for the K-heavy 128x128 GEMMs
     const int nwg = p.tiles_m * p.tiles_n;
     p.nwg0 = nwg;
     hipLaunchKernelGGL(kern, dim3(nwg * (p.ksplit > 1 ? p.ksplit : 1) * (p.dual ? 2 : 1)), dim3(64 * WM * WN), LDS, st, p);
@@ -1257,24 +1178,18 @@ static int launch_anti(GemmParams p, hipStream_t st) {
     // profiles/r06_order_ab.txt) -- since the 16-bit outputs are stored non-temporally this beats the W-resident
     // groups of 4 n-tiles (mode 4) that round 2 chose: same box, round-robin, 87.31 -> 86.62 ms per pipelined bench step (and 91.8 -> 91.1 on the slowest
     // box seen); in a traced single-stream step proj + fc2 go 327 -> 317 us per launch, fc1 524 -> 532, qkv stays (profiles/r06_order_ab.txt).  Mode 4 keeps
-    // the one shape it was found on: N = 9216 (36 n-tiles, the cross-attention K|V projection: +8 %).  SPRC_GEMM_ORDER forces one mode everywhere (A/B).
-    static const int order = env_int("SPRC_GEMM_ORDER", -1);
-    p.order = order >= 0 ? order : (p.tiles_n >= 32 ? 4 : 0);
+    // the one shape it was found on: N = 9216 (36 n-tiles, the cross-attention K|V projection: +8 %).
+    p.order = p.tiles_n >= 32 ? 4 : 0;
     p.nwg0 = p.tiles_m * p.tiles_n;
-    // one workgroup per CU that walks its tiles (SPRC_GEMM_PERSIST=0: one workgroup per tile, the A/B switch).  Same box, pipelined bench step:
+    // one workgroup per CU that walks its tiles (measured against one workgroup per tile).  Same box, pipelined bench step:
     // 90.13 / 90.24 ms (the kernel without the tile loop) -> 90.48 / 90.38 (this kernel, one workgroup per tile) -> 89.23 / 89.40 (persistent);
     // the class time of the serial, instrumented steps does not move (79.5 ms): what is saved are workgroup hand-overs while the Q-Former's
     // side-stream kernels compete for CUs (profiles/r05_persist_ab.txt)
-    static const int persist = env_int("SPRC_GEMM_PERSIST", 1);
     const int total = p.nwg0 * (p.dual ? 2 : 1), ncu = num_cus(st) & ~7;
-    hipLaunchKernelGGL(kern, dim3(persist && ncu > 0 && total > ncu ? ncu : total), dim3(512), LDS, st, p);
+    hipLaunchKernelGGL(kern, dim3(ncu > 0 && total > ncu ? ncu : total), dim3(512), LDS, st, p);
     SPRC_CHECK_LAUNCH("sprc_gemm(anti)");
     return SPRC_OK;
 }
-
-// duo kernel (gemm_duo.hpp; its instantiations live in gemm_duo.hip): 16-bit operands, out kind 0 = the operands' 16-bit type, 1 = fp32,
-// 2 = SPRC_F16X3 split rows (fp16 operands).  SPRC_EUNSUPPORTED: no such instantiation -- the caller falls back to the other kernels.
-int gemm_duo_launch(bool f16, int out_kind, int act, const GemmParams& p, hipStream_t st);
 
 // The kernels address a tile with 32-bit offsets from its first row: the rows of one (<= 256-row) tile must span < 4 GiB.
 static bool fits_u32(const GemmParams& p) {
@@ -1308,14 +1223,6 @@ static int launch(const GemmParams& p, hipStream_t st) {
     }
     const int keff = MIX ? p.K + p.k8 / 2 : p.K;                // reduction length in units of 16-bit elements (time ~ bytes of a row)
     int cfg = forced;
-    if constexpr (sizeof(T) == 2 && !MAX32 && !MIX && !std::is_same<OutT, fp8_t>::value) {
-        static const int duo = env_int("SPRC_GEMM_DUO", 0);       // 1: every eligible product on the duo kernel (A/B switch)
-        if (duo == 1 && p.ksplit <= 1 && p.K % 32 == 0) {
-            constexpr int ok = std::is_same<OutT, float>::value ? 1 : std::is_same<OutT, f16x3_t>::value ? 2 : 0;
-            const int rc = gemm_duo_launch(std::is_same<T, f16_t>::value, ok, ACT, p, st);
-            if (rc != SPRC_EUNSUPPORTED) return rc;
-        }
-    }
     if constexpr (sizeof(T) <= 2) {
         if (cfg == 0) {
             // Cost model in units of one 256x256xK tile on a CU (measured on MI355X, tools/gemm_shapes.py):
@@ -1339,8 +1246,7 @@ static int launch(const GemmParams& p, hipStream_t st) {
                 return 0.7 * (double)full + (last == 0 ? 0.0 : last <= ncu ? 0.42 : 0.7);
             };
             const double cA = cost128(p.M), cB = cost256(p.M);
-            static const int peel = env_int("SPRC_GEMM_PEEL", 1);
-            const bool can_peel = peel && !MAX32 && !p.dual && p.M > 256 && p.a_shift < 0 && p.c_shift < 0;
+            const bool can_peel = !MAX32 && !p.dual && p.M > 256 && p.a_shift < 0 && p.c_shift < 0;
             double cC = 1e30;
             int Mm = 0;
             if (can_peel) {
@@ -1360,23 +1266,13 @@ static int launch(const GemmParams& p, hipStream_t st) {
                 pt.A = p.A + (int64_t)Mm * p.lda_b;
                 pt.C = reinterpret_cast<char*>(p.C) + (int64_t)Mm * p.ldc * (MAX32 ? 4 : (int64_t)sizeof(OutT));
                 if (p.resid != nullptr) pt.resid = p.resid + (int64_t)Mm * p.ldr;
-                // SPRC_GEMM_SIDE=1 (A/B switch, OFF by default): the remainder rows (disjoint from the main launch's) go to a library-owned
-                // side stream, forked before and joined after the main launch, so that their handful of latency-bound workgroups
-                // (11-16 us per launch, 1.8 ms of a bench step when run behind the main kernel) could start as soon as CUs of the main
-                // kernel's last round fall idle.  Measured on MI355X: the step got SLOWER, 89.7 -> 93.0 ms (same box, twice) -- the two
-                // extra event pairs per product and the remainder workgroups taking CUs from the main kernel's first round cost more
-                // than the 1.8 ms they could hide.
-                SideStream* ss = side_stream();
-                hipStream_t sr = st;
-                if (ss != nullptr) {
-                    (void)hipEventRecord(ss->fork, st);
-                    (void)hipStreamWaitEvent(ss->st, ss->fork, 0);
-                    sr = ss->st;
-                }
+                // (The remainder rows -- disjoint from the main launch's -- were also run on a library-owned side stream, forked before and
+                // joined after the main launch, so that their handful of latency-bound workgroups (11-16 us per launch, 1.8 ms of a bench step
+                // when run behind the main kernel) could start as soon as CUs of the main kernel's last round fall idle.  Measured on MI355X:
+                // the step got SLOWER, 89.7 -> 93.0 ms (same box, twice) -- the two extra event pairs per product and the remainder workgroups
+                // taking CUs from the main kernel's first round cost more than the 1.8 ms they could hide.  Removed.)
                 const int rc = launch_anti<T, OutT, ACT, MAX32, MIX>(pm, st);
                 if (rc != SPRC_OK) return rc;
-                const int rr = [&]() -> int {
-                hipStream_t st = sr;                 // (shadows the caller's stream inside the remainder launches)
                 // remainder rows: a long reduction on a handful of workgroups is latency-bound (11 WGs x 96 K-tiles = 77 us
                 // for the ViT fc2) -> split K over 8 workgroups per tile into caller scratch and reduce in a fixed order
                 constexpr int S = 8;
@@ -1385,9 +1281,8 @@ static int launch(const GemmParams& p, hipStream_t st) {
                     GemmParams ps = pt;
                     ps.C = p.scratch; ps.ldc = p.N; ps.bias = nullptr; ps.resid = nullptr; ps.ldr = 0; ps.w_scale = nullptr;
                     ps.ksplit = S; ps.split_stride = (int64_t)rem * p.N;
-                    static const int ring = env_int("SPRC_GEMM_RING", 1);   // a handful of workgroups: ring of 4 stages (0: two stages, A/B)
-                    const int rs = ring ? launch_cfg<T, float, SPRC_ACT_NONE, false, 2, 2, 2, 2, 1, 4, MIX>(ps, st)
-                                        : launch_cfg<T, float, SPRC_ACT_NONE, false, 2, 2, 2, 2, 2, 2, MIX>(ps, st);
+                    // a handful of workgroups: ring of 4 stages
+                    const int rs = launch_cfg<T, float, SPRC_ACT_NONE, false, 2, 2, 2, 2, 1, 4, MIX>(ps, st);
                     if (rs != SPRC_OK) return rs;
                     const int64_t n = (int64_t)rem * (p.N / 4);
                     hipLaunchKernelGGL((splitk_reduce_kernel<OutT, ACT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -1397,17 +1292,9 @@ static int launch(const GemmParams& p, hipStream_t st) {
                     return SPRC_OK;
                 }
                 if constexpr (sizeof(T) == 2 && !MAX32) {
-                    static const int ring = env_int("SPRC_GEMM_RING", 1);
-                    if (((rem + 127) / 128) * tn128 <= ncu)
-                        return ring ? launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 2, 4, MIX>(pt, st) : launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 4, 2, MIX>(pt, st);
+                    if (((rem + 127) / 128) * tn128 <= ncu) return launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 2, 4, MIX>(pt, st);
                 }
                 return launch_cfg<T, OutT, ACT, MAX32, 2, 2, 2, 2, 2, 2, MIX>(pt, st);
-                }();
-                if (ss != nullptr) {
-                    (void)hipEventRecord(ss->join, sr);
-                    (void)hipStreamWaitEvent(st, ss->join, 0);
-                }
-                return rr;
             }
             cfg = cB <= cA ? 4 : 2;
             // a 128x128 grid that cannot even give every CU one workgroup is latency-bound (12-48 K-tiles on a fraction of the
@@ -1425,9 +1312,8 @@ static int launch(const GemmParams& p, hipStream_t st) {
     if constexpr (sizeof(T) == 2 && !MAX32) {
         if (cfg == 1) {                                     // 64 x 64 tile: small latency-bound products; ring of 4 stages (64 KB) or 2 (32 KB)
             // (the ring's 64 KB leave two workgroups per CU: only for grids that fit then -- 768 workgroups ran 5 % slower on it)
-            static const int ring = env_int("SPRC_GEMM_RING", 1);
             const int64_t nwg64 = (p.dual ? 2 : 1) * (int64_t)((p.M + 63) / 64) * ((p.N + 63) / 64);
-            return ring && nwg64 <= 2 * num_cus(st) ? launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 2, 4, MIX>(p, st)
+            return nwg64 <= 2 * num_cus(st) ? launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 2, 4, MIX>(p, st)
                                                   : launch_cfg<T, OutT, ACT, MAX32, 2, 2, 1, 1, 4, 2, MIX>(p, st);
         }
     }

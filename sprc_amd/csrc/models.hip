@@ -62,8 +62,7 @@ static int gemm2(hipStream_t st, int dt, int out_dt, int M, int N, int K, const 
 
 // y = LN(x [+ add16]); sum32 (optional) receives x + add16 (the residual-stream update of a pre-LN block)
 static int lnorm(hipStream_t st, int dt, int M, int D, const float* x, const float* gam, const float* bet, float eps,
-                 float* y32, void* y16, sprc_rowmap map = ID_MAP, const void* add16 = nullptr, float* sum32 = nullptr,
-                 float y16_scale = 0.f) {
+                 float* y32, void* y16, sprc_rowmap map = ID_MAP, float y16_scale = 0.f) {
     const int64_t ld16 = dt == SPRC_F16X3 ? 2 * (int64_t)D : D;          // fp16 units: a split row is 4 D bytes
     sprc_layernorm_args a;
     memset(&a, 0, sizeof(a));
@@ -72,8 +71,6 @@ static int lnorm(hipStream_t st, int dt, int M, int D, const float* x, const flo
     a.gamma = gam; a.beta = bet; a.eps = eps;
     a.y32 = y32; a.ld32 = D; a.ymap = map;
     a.y16 = y16; a.ld16 = ld16;
-    a.add16 = add16; a.ld_add = D;
-    a.sum32 = sum32; a.ld_sum = D;
     a.y16_scale = y16_scale;
     return sprc_layernorm(&a, st);
 }
@@ -106,16 +103,12 @@ static int attn(hipStream_t st, int dt, int B, int H, int Tq, int Tk, int dh, co
     return sprc_attention(&a, st);
 }
 
-// SPRC_FUSE_ADD=1 (default 0): fold the residual adds into the LayerNorm kernels (branch GEMMs write fp16 deltas, see
-// sprc_layernorm_args.add16).  Measured on MI355X (tools/fuse_ab.sh): GEMM class 83.9 -> 78.5 ms per step (872 -> 932
+// The residual adds stay in the branch GEMMs' fp32 + residual epilogues.  Folding them into the LayerNorm kernels (branch GEMMs
+// writing fp16 deltas, sprc_layernorm_args.add16) was measured on MI355X and removed: GEMM class 83.9 -> 78.5 ms per step (872 -> 932
 // TFLOP/s) but the LayerNorms 5.8 -> 10.5 ms -- the same 14 B per element cross HBM either way, they only move from the
 // GEMM epilogue burst to the row kernels -- i.e. +0.3 % images/s, while the fp16 rounding of every branch output (2^-11
 // relative, not averaged over K like the bf16 operand roundings) takes the full-depth ViT-g cosine error from 4.3e-4 to
-// 1.1e-3, over the 1e-3 bar.  Kept as an A/B switch; off.
-static bool fuse_add_enabled(int which = 1) {            // bit 0: ViT blocks, bit 1: Q-Former layers
-    static const int on = [] { const char* e = getenv("SPRC_FUSE_ADD"); return e ? atoi(e) : 0; }();
-    return (on & which) != 0;
-}
+// 1.1e-3, over the 1e-3 bar.
 
 #define RUN(x)                      \
     do {                            \
@@ -186,10 +179,6 @@ static X3Layouts x3_layouts(int cm) {
 // self-attention (output projection, cross-attention, FFNs, LayerNorms) on those rows alone.  The other rows of x32 / x16 keep the
 // previous layer's values.  Pass 1 of the fusion is read on its 32 query rows (align_prompt.py:341-346), pass 2 on the one [CLS] row
 // (:348-350), the text passes on row 0, the ITM pass on its query rows: work nobody reads, 0.5 ms of kernel time per bench step.
-static bool qf_dead_rows_enabled() {
-    static const int on = [] { const char* e = getenv("SPRC_QF_DEAD"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
 
 static int qf_stack(const sprc_qformer_model* m, hipStream_t st, QfBufs& q, int B, int S, const KvSrc* kvs,
                     const float* mask, float* x32, void* x16, int cm, int need_lo = 0, int need_n = 0) {
@@ -205,9 +194,6 @@ static int qf_stack(const sprc_qformer_model* m, hipStream_t st, QfBufs& q, int 
     const size_t es = dtype_size(dt);
     const sprc_rowmap qmap = {Lq, S, 0}, tmap = {S - Lq, S, Lq};
     const bool split = with_enc && S > Lq;         // rows [:Lq] and [Lq:] take different paths
-    // SPRC_FUSE_ADD=1: the post-LN residual adds (Qformer.py:294,380) ride on the LayerNorm kernels (sprc_layernorm add16),
-    // the branch GEMMs write fp16 instead of running an fp32 + residual epilogue.  Off by default (see fuse_add_enabled).
-    const bool fuse_add = dt == SPRC_BF16 && fuse_add_enabled(2);
     // y = act(in . W^T + b) of layer kind `kind` over `width` input columns, into a compute-dtype (or x3) buffer
     auto lin = [&](int kind, int rows, int N, int width, const void* in, int64_t lda, const sprc_linear& w, int odt, void* out,
                    int64_t ldc, int act, sprc_rowmap amap, sprc_rowmap cmap) -> int {
@@ -217,15 +203,11 @@ static int qf_stack(const sprc_qformer_model* m, hipStream_t st, QfBufs& q, int 
     // a = LN(dense(in) + res): branch GEMM of layer kind `kind` over `width` input columns, post-LN into (o32, o16)
     auto branch = [&](int kind, int rows, int width, int64_t lda, const void* in, const sprc_linear& w, const float* res,
                       const float* lw, const float* lb, float* o32, void* o16, sprc_rowmap amap, sprc_rowmap cmap) -> int {
-        if (fuse_add) {         // the branch output goes out as fp16 into a16 (dead here) and is added by the LN
-            RUN(gemm(st, dt, SPRC_F16, rows, Hd, width, in, lda, w, q.a16, Hd, SPRC_ACT_NONE, nullptr, 0, amap, cmap));
-            return lnorm(st, dt, rows, Hd, res, lw, lb, m->ln_eps, o32, o16, cmap, q.a16);
-        }
         RUN(gemm(st, dt, SPRC_F32, rows, Hd, width, in, lda, w, q.t32, Hd, SPRC_ACT_NONE, res, Hd, amap, cmap, nullptr, 0,
                  nullptr, wld(kind, width), k8of(kind, width)));
         return lnorm(st, adt, rows, Hd, q.t32, lw, lb, m->ln_eps, o32, o16, cmap);
     };
-    const bool prune = qf_dead_rows_enabled() && !fuse_add && need_n > 0 && need_n < S && (need_n & (need_n - 1)) == 0 &&
+    const bool prune = need_n > 0 && need_n < S && (need_n & (need_n - 1)) == 0 &&
                        (with_enc ? (split && need_lo == 0 && need_n == Lq) : true);
     for (int l = 0; l < m->n_layers; ++l) {
         const sprc_qf_layer& L = m->layers[l];
@@ -276,17 +258,10 @@ static int qf_stack(const sprc_qformer_model* m, hipStream_t st, QfBufs& q, int 
                 // The hidden activations keep the rows' natural positions in q.ffn [R, F].
                 RUN(gemm2(st, dt, fdt, Rq, F, Hd, q.a16, KH, L.ffn_q_in, L.ffn_t_in, q.ffn, KF, SPRC_ACT_GELU, nullptr, 0,
                           qmap, tmap, qmap, tmap, wld(SPRC_X3_FFN_IN, Hd), k8of(SPRC_X3_FFN_IN, Hd)));
-                if (fuse_add) {
-                    RUN(gemm2(st, dt, SPRC_F16, Rq, Hd, F, q.ffn, F, L.ffn_q_out, L.ffn_t_out, q.a16, Hd, SPRC_ACT_NONE, nullptr, 0, qmap,
-                              tmap, qmap, tmap));
-                    RUN(lnorm(st, dt, Rq, Hd, q.a32, L.ffn_q_ln_w, L.ffn_q_ln_b, m->ln_eps, x32, x16, qmap, q.a16));
-                    RUN(lnorm(st, dt, Rq, Hd, q.a32, L.ffn_t_ln_w, L.ffn_t_ln_b, m->ln_eps, x32, x16, tmap, q.a16));
-                } else {
-                    RUN(gemm2(st, dt, SPRC_F32, Rq, Hd, F, q.ffn, KF, L.ffn_q_out, L.ffn_t_out, q.t32, Hd, SPRC_ACT_NONE,
-                              q.a32, Hd, qmap, tmap, qmap, tmap, wld(SPRC_X3_FFN_OUT, F), k8of(SPRC_X3_FFN_OUT, F)));
-                    RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_q_ln_w, L.ffn_q_ln_b, m->ln_eps, x32, x16, qmap));
-                    RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_t_ln_w, L.ffn_t_ln_b, m->ln_eps, x32, x16, tmap));
-                }
+                RUN(gemm2(st, dt, SPRC_F32, Rq, Hd, F, q.ffn, KF, L.ffn_q_out, L.ffn_t_out, q.t32, Hd, SPRC_ACT_NONE,
+                          q.a32, Hd, qmap, tmap, qmap, tmap, wld(SPRC_X3_FFN_OUT, F), k8of(SPRC_X3_FFN_OUT, F)));
+                RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_q_ln_w, L.ffn_q_ln_b, m->ln_eps, x32, x16, qmap));
+                RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_t_ln_w, L.ffn_t_ln_b, m->ln_eps, x32, x16, tmap));
             } else {
                 RUN(lin(SPRC_X3_FFN_IN, Rq, F, Hd, q.a16, KH, L.ffn_q_in, fdt, q.ffn, KF, SPRC_ACT_GELU, rq, ID_MAP));
                 RUN(branch(SPRC_X3_FFN_OUT, Rq, F, KF, q.ffn, L.ffn_q_out, q.a32, L.ffn_q_ln_w, L.ffn_q_ln_b, x32, x16, ID_MAP, rq));
@@ -429,12 +404,8 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
                         (char*)v.ctx + r0 * D * es, (char*)v.mlp + r0 * (size_t)F * es,
                         (char*)v.pout + (i == 0 ? 0 : align_up(pout_bytes / 2, 256)), raw + r0 * D};
     }
-    // SPRC_FUSE_ADD=1: x += proj(..) and x += fc2(..) (eva_vit.py:178-179, clip_vit.py:137-138) are folded into the LayerNorm
-    // that reads x next: the branch GEMM writes its output as fp16 into the h buffer (dead at that point; the LN overwrites
-    // it in place with its bf16 result) and the LN kernel adds it to the fp32 residual stream (sum32 = x) before the
-    // statistics.  Off by default (see fuse_add_enabled: no net gain, and it costs parity).
+    // x += proj(..) and x += fc2(..) (eva_vit.py:178-179, clip_vit.py:137-138): fp32 + residual epilogues (see the note above RUN)
     const bool fp8 = m->fp8 != 0, fp8_qkv = m->fp8 == SPRC_FP8_ALL;
-    const bool fuse_add = dt == SPRC_BF16 && !fp8 && fuse_add_enabled(1);
     SPRC_REQUIRE(m->fp8 == 0 || m->fp8 == SPRC_FP8_ALL || m->fp8 == SPRC_FP8_MLP, "sprc_vit_forward: fp8 = %d", m->fp8);
     SPRC_REQUIRE(!fp8 || (is16(dt) && D % 128 == 0 && F % 128 == 0), "sprc_vit_forward: the fp8 path needs a 16-bit model with width, mlp %% 128 == 0");
     SPRC_REQUIRE(!(fp8 && m->calib_amax), "sprc_vit_forward: calibrate on the 16-bit model, not on the fp8 one");
@@ -449,7 +420,7 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
                 // h (bf16-sized) holds the fp8 operand: half its bytes, leading dimension D bytes.
                 const Fp8Scales s_qkv{L.qkv_ws, L.s_ln1, 0.f}, s_fc1{L.fc1_ws, L.s_ln2, 1.0f / L.s_mlp}, s_fc2{L.fc2_ws, L.s_mlp, 0.f};
                 if (fp8_qkv) {
-                    RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h, ID_MAP, nullptr, nullptr, 1.0f / L.s_ln1));
+                    RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h, ID_MAP, 1.0f / L.s_ln1));
                     RUN(gemm(q.ps, SPRC_FP8, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D, SPRC_ACT_NONE, nullptr, 0, ID_MAP, ID_MAP,
                              nullptr, 0, &s_qkv));
                 } else {
@@ -459,44 +430,27 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
                 RUN(attn(q.ps, dt, q.Bp, m->heads, T, T, m->head_dim, q.qkv, 3 * D, q.qkv + D * es, 3 * D, q.qkv + 2 * D * es, 3 * D,
                          q.ctx, D, nullptr, scale));
                 RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D, SPRC_ACT_NONE, q.x, D));
-                RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h, ID_MAP, nullptr, nullptr, 1.0f / L.s_ln2));
+                RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h, ID_MAP, 1.0f / L.s_ln2));
                 RUN(gemm(q.ps, SPRC_FP8, SPRC_FP8, q.Mp, F, D, q.h, D, L.fc1, q.mlp, F, m->act, nullptr, 0, ID_MAP, ID_MAP, nullptr, 0, &s_fc1));
                 RUN(gemm(q.ps, SPRC_FP8, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D, SPRC_ACT_NONE, q.x, D, ID_MAP, ID_MAP, q.scratch,
                          scratch_bytes, &s_fc2));
                 continue;
             }
-            if (fuse_add) {
-                const bool pend = l > 0;                    // fc2 output of the previous layer waits in h
-                RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h, ID_MAP, pend ? q.h : nullptr,
-                          pend ? q.x : nullptr));
-            } else {
-                RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h));
-            }
+            RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h));
             if (calib) RUN(sprc_absmax_16(q.h, (size_t)q.Mp * D, dt, calib + l * 3 + 0, q.ps));
             RUN(gemm(q.ps, dt, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D));
             RUN(attn(q.ps, dt, q.Bp, m->heads, T, T, m->head_dim, q.qkv, 3 * D, q.qkv + D * es, 3 * D, q.qkv + 2 * D * es, 3 * D,
                      q.ctx, D, nullptr, scale));
-            if (fuse_add) {
-                RUN(gemm(q.ps, dt, SPRC_F16, q.Mp, D, D, q.ctx, D, L.proj, q.h, D));
-                RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h, ID_MAP, q.h, q.x));
-            } else {
-                RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D, SPRC_ACT_NONE, q.x, D));
-                RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h));
-            }
+            RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D, SPRC_ACT_NONE, q.x, D));
+            RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h));
             if (calib) RUN(sprc_absmax_16(q.h, (size_t)q.Mp * D, dt, calib + l * 3 + 1, q.ps));
             RUN(gemm(q.ps, dt, dt, q.Mp, F, D, q.h, D, L.fc1, q.mlp, F, m->act));
             if (calib) RUN(sprc_absmax_16(q.mlp, (size_t)q.Mp * F, dt, calib + l * 3 + 2, q.ps));
-            if (fuse_add) {
-                RUN(gemm(q.ps, dt, SPRC_F16, q.Mp, D, F, q.mlp, F, L.fc2, q.h, D, SPRC_ACT_NONE, nullptr, 0, ID_MAP, ID_MAP, q.scratch,
-                         scratch_bytes));
-            } else {
-                RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D, SPRC_ACT_NONE, q.x, D, ID_MAP, ID_MAP, q.scratch,
-                         scratch_bytes));
-            }
+            RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D, SPRC_ACT_NONE, q.x, D, ID_MAP, ID_MAP, q.scratch,
+                     scratch_bytes));
         }
     }
     if (m->pre_ln_out != nullptr) {
-        SPRC_REQUIRE(!fuse_add, "sprc_vit_forward: pre_ln_out is not available with SPRC_FUSE_ADD");
         for (int i = 0; i < nparts; ++i) {
             const size_t r0 = (size_t)(parts[i].x - v.x);
             SPRC_REQUIRE(hipMemcpyAsync(m->pre_ln_out + r0, parts[i].x, (size_t)parts[i].Mp * D * sizeof(float), hipMemcpyDeviceToDevice,
@@ -504,8 +458,7 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
         }
     }
     for (int i = 0; i < nparts; ++i)
-        RUN(lnorm(parts[i].ps, dt, parts[i].Mp, D, parts[i].x, m->ln_vision_w, m->ln_vision_b, m->ln_vision_eps, parts[i].raw, nullptr,
-                  ID_MAP, fuse_add && m->depth > 0 ? parts[i].h : nullptr));
+        RUN(lnorm(parts[i].ps, dt, parts[i].Mp, D, parts[i].x, m->ln_vision_w, m->ln_vision_b, m->ln_vision_eps, parts[i].raw, nullptr));
     if (split) {
         (void)hipEventRecord(ev_join, st2);
         (void)hipStreamWaitEvent(st, ev_join, 0);

@@ -26,6 +26,20 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.sprc_last_error(), bytes)
 
 
+def test_native_library_has_no_hidden_switches():
+    """The HIP sources read exactly the documented environment variables and carry no preprocessor conditionals:
+    a measured alternative is removed, not kept behind a switch that no test runs."""
+    files = sorted(f for f in (ROOT / "sprc_amd" / "csrc").glob("*") if f.suffix in (".hip", ".hpp", ".h", ".cpp"))
+    assert files
+    names = set()
+    for f in files:
+        text = f.read_text()
+        names |= set(re.findall(r'\b(?:getenv|env_int)\(\s*"([A-Za-z0-9_]+)"', text))
+        conditionals = [line for line in text.splitlines() if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line)]
+        assert not conditionals, f"{f.name}: {conditionals}"
+    assert names == {"SPRC_VIT_STREAMS", "SPRC_GEMM_TILE", "SPRC_GEMM_DEBUG", "SPRC_GEMM_STAMP_MASK", "SPRC_GEMM_STAMP_WG"}
+
+
 def test_argument_validation_reports_errors_without_a_gpu():
     import ctypes as C
     from sprc_amd import _lib as L

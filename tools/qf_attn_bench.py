@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Q-Former attention launches of one bench step, timed alone: tools/qf_attn_bench.py  (SPRC_ATTN_SMALL_NW=1|2|4 for A/B)"""
+"""Q-Former attention launches of one bench step, timed alone: tools/qf_attn_bench.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sprc_amd import engine as E
@@ -19,6 +19,5 @@ def run(B, Tq, Tk, masked, x3=False, ldkv=None):
     us = e0.elapsed_time(e1) / 50 * 1e3
     mb = B * H * dh * 2 * (2 * Tq + 2 * Tk) / 1e6
     print(f"B {B:4d} Tq {Tq:3d} Tk {Tk:3d} mask {int(masked)}: {us:7.1f} us   ({mb:.0f} MB -> {mb / us / 1e3 * 1e3:.0f} GB/s)")
-print("SPRC_ATTN_SMALL_NW =", os.environ.get("SPRC_ATTN_SMALL_NW", "4 (default)"), " SPRC_ATTN_CROSS =", os.environ.get("SPRC_ATTN_CROSS", "3 (default)"))
 run(233, 64, 64, True); run(233, 32, 257, False); run(128, 32, 32, False); run(128, 32, 257, False)
 run(233, 32, 257, False, ldkv=9216); run(128, 32, 257, False, ldkv=9216)
