@@ -1,6 +1,6 @@
 // gemm_impl.hpp -- C = epilogue(A[M,K] . W[N,K]^T) on gfx950 matrix cores: kernels, launchers and the per-operand-type
-// dispatcher.  Included by gemm.hip (C entry points + bf16 operands), gemm_f32.hip and gemm_fp8.hip: one translation unit per
-// operand type, so the three sets of template instantiations compile in parallel (one TU took six minutes).
+// dispatcher.  Included by gemm.hip (C entry points + bf16 operands), gemm_f16.hip, gemm_f16e.hip (split-precision fp16), gemm_fp8.hip and
+// gemm_f32.hip: one translation unit per operand type, so the five sets of template instantiations compile in parallel (one TU took six minutes).
 //
 // Replaces every nn.Linear / F.linear / conv-as-GEMM on the SPRC retrieval path (see sprc.h).
 // Both operands are K-contiguous ("B^T" form), so A and W fragments are read the same way.
@@ -159,10 +159,11 @@ __device__ __forceinline__ void buffer_load_lds16(__amdgpu_buffer_rsrc_t rs, cha
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds_dst, 16, voffset, soffset, 0, 0);     // default cache policy (nt: +3-4 ms per step)
 }
 
+template <int I> using ic = std::integral_constant<int, I>;
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
+        f(ic<I>{});
         static_for<I + 1, N>(f);
     }
 }
@@ -241,12 +242,12 @@ __device__ __forceinline__ void pipe_ktile_mx(uint32_t a_base, uint32_t b_base, 
             static_for<0, TN>([&](auto i) { fb[pr][k][decltype(i)::value] = lds_read128<decltype(i)::value * 32 * KT_BYTES>(bn); });
         });
     };
-    read_pair(std::integral_constant<int, 0>{});
+    read_pair(ic<0>{});
     static_for<0, 2>([&](auto p_) {
         constexpr int pr = decltype(p_)::value;
-        if constexpr (pr == 0) read_pair(std::integral_constant<int, 1>{});
-        issue(std::integral_constant<int, 2 * pr>{});
-        issue(std::integral_constant<int, 2 * pr + 1>{});
+        if constexpr (pr == 0) read_pair(ic<1>{});
+        issue(ic<2 * pr>{});
+        issue(ic<2 * pr + 1>{});
         if constexpr (pr == 0) wait_lgkmcnt<2 * (TM + TN)>();
         else wait_lgkmcnt<0>();
         __builtin_amdgcn_s_setprio(1);
@@ -347,9 +348,45 @@ __device__ __forceinline__ kparams_t kernarg_params() {
 // The caller guarantees every wave is done reading operand tiles from LDS (a barrier after the K loop).
 constexpr int EPI_STRIP_BYTES(int TN) { return 32 * (32 * TN + 4) * 4; }
 
+// Accumulator value -> stored value, the one statement of the chain: dequantise, bias, activation, residual, fp8 output scale.  The terms are
+// CALLABLES, evaluated only under their flag and where the chain uses them: the scalar callers read them through pointers that may be null, and with
+// the terms fetched ahead as values hipcc turns the chain into selects (tried: 600 more instructions per kernel, other multiplies and adds fuse).
+// FAST_GELU / FAST_QGELU: the v_exp / v_rcp forms.  The in-kernel epilogue takes both for 1- and 2-byte operands and neither for fp32; the split-K
+// reduction has always paired gelu_fast with the EXACT quick_gelu, whatever the operand type -- kept as it is (no product launch combines QuickGELU
+// with split-K: the pair is reachable only through the C ABI).
+// Forced inline and in this order: hipcc contracts a * b + c across statements, and which multiplies and adds fuse decides the last bit.
+template <int ACT, bool FAST_GELU, bool FAST_QGELU, typename OutT, typename S, typename B, typename R>
+__device__ __forceinline__ float epi_value(float v, bool scaled, S scale, bool has_bias, B bias, bool has_resid, R resid, float out_scale) {
+    if (scaled) v *= scale();
+    if (has_bias) v += bias();
+    if constexpr (ACT == SPRC_ACT_GELU) v = FAST_GELU ? gelu_fast(v) : gelu_erf(v);
+    if constexpr (ACT == SPRC_ACT_QUICKGELU) v = FAST_QGELU ? quick_gelu_fast(v) : quick_gelu(v);
+    if (has_resid) v += resid();
+    if constexpr (std::is_same<OutT, fp8_t>::value) v *= out_scale;
+    return v;
+}
+
+// the epilogue's vector path: 4 outputs of a row per lane, every vector it touches aligned
+template <typename OutT>
+__device__ __forceinline__ bool epi_vec_ok(const GemmParams& p) {
+    return (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.resid == nullptr || p.ldr % 4 == 0) &&
+           ((uintptr_t)p.C % (4 * sizeof(OutT)) == 0) && ((uintptr_t)p.bias % 16 == 0) && ((uintptr_t)p.resid % 16 == 0);
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+}
+
 template <typename T, typename OutT, int ACT, bool MAX32, int TM, int TN>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)[TM][TN], int cm0, int cn0, int wr, int wc,
                                               int r32, int half, bool vec_ok, char* smem, int wave) {
+    constexpr bool FAST = sizeof(T) <= 2;     // activations of 1- and 2-byte operands: the v_exp / v_rcp forms (fp32 operands: erf, IEEE division)
     if constexpr (!MAX32) {
         if (vec_ok) {
             // W = columns per lane.  4: one 16-B strip read, 16-B (fp32) / 8-B (16-bit) / 4-B (fp8) stores.  8 (outputs narrower than
@@ -434,17 +471,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
 #pragma unroll
                         for (int j = 0; j < NV; ++j)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {       // element-wise on purpose: vector adds become v_pk_add_f32 (slower)
-                            if (scaled) v[j][e] *= sv[j][e];
-                            v[j][e] += bv[j][e];
-                            if constexpr (ACT == SPRC_ACT_GELU) {
-                                if constexpr (sizeof(T) <= 2) v[j][e] = gelu_fast(v[j][e]);
-                                else v[j][e] = gelu_erf(v[j][e]);
-                            }
-                            if constexpr (ACT == SPRC_ACT_QUICKGELU) v[j][e] = sizeof(T) <= 2 ? quick_gelu_fast(v[j][e]) : quick_gelu(v[j][e]);
-                            if constexpr (RES) v[j][e] += rv[mi & 1][it][j][e];
-                            if constexpr (std::is_same<OutT, fp8_t>::value) v[j][e] *= p.out_scale;
-                        }
+                        for (int e = 0; e < 4; ++e)         // element-wise on purpose: vector adds become v_pk_add_f32 (slower)
+                            v[j][e] = epi_value<ACT, FAST, FAST, OutT>(v[j][e], scaled, [&] { return sv[j][e]; }, true, [&] { return bv[j][e]; },
+                                                                       RES, [&] { return rv[mi & 1][it][j][e]; }, p.out_scale);
                         const int row = block_row(mi, it);
                         if (!(row < p.M && col_ok)) continue;
                         OutT* const dst = cbase + (__umul24((uint32_t)(mrow(row) - row0m), ldc32) + (uint32_t)col);
@@ -461,9 +490,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
             };
             if constexpr (sizeof(OutT) < 4) {
                 const bool wide_ok = (p.N % 8 == 0) && (p.ldc % 8 == 0) && ((uintptr_t)p.C % 16 == 0);
-                if (wide_ok) { vec_path(std::integral_constant<int, 8>{}); return; }
+                if (wide_ok) { vec_path(ic<8>{}); return; }
             }
-            vec_path(std::integral_constant<int, 4>{});
+            vec_path(ic<4>{});
             return;
         }
     }
@@ -494,16 +523,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
                     for (int r = 0; r < 16; ++r) {
                         const int col = cn0 + (wc * TN + ni) * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
                         if (!(row_ok && col < p.N)) continue;
-                        float v = acc[mi][ni][r];
-                        if (p.w_scale != nullptr) v *= p.a_scale * p.w_scale[col];
-                        v += (p.bias ? p.bias[col] : 0.f);
-                        if constexpr (ACT == SPRC_ACT_GELU) {
-                            if constexpr (sizeof(T) <= 2) v = gelu_fast(v);
-                            else v = gelu_erf(v);
-                        }
-                        if constexpr (ACT == SPRC_ACT_QUICKGELU) v = sizeof(T) <= 2 ? quick_gelu_fast(v) : quick_gelu(v);
-                        if (rrow != nullptr) v += rrow[col];
-                        if constexpr (std::is_same<OutT, fp8_t>::value) v *= p.out_scale;
+                        const float v = epi_value<ACT, FAST, FAST, OutT>(acc[mi][ni][r], p.w_scale != nullptr, [&] { return p.a_scale * p.w_scale[col]; }, true,
+                                                                         [&] { return p.bias ? p.bias[col] : 0.f; }, rrow != nullptr, [&] { return rrow[col]; }, p.out_scale);
                         store_out1<OutT>(crow + col, v, p.N, col);
                     }
             }
@@ -585,8 +606,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(GemmParams p) {
     const int a_off = (wr * TM * 32 + r32) * KT_BYTES, b_off = BM * KT_BYTES + (wc * TN * 32 + r32) * KT_BYTES;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
     const uint32_t c0 = (uint32_t)((half ^ sw) << 4);
-    const bool vec_ok = (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.resid == nullptr || p.ldr % 4 == 0) &&
-                        ((uintptr_t)p.C % (4 * sizeof(OutT)) == 0) && ((uintptr_t)p.bias % 16 == 0) && ((uintptr_t)p.resid % 16 == 0);
+    const bool vec_ok = epi_vec_ok<OutT>(p);
 
     static_for<0, NS - 1>([&](auto d_) {                        // K-tiles 0 .. NS-2
         constexpr int d = decltype(d_)::value;
@@ -598,12 +618,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(GemmParams p) {
 
     {
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        zero_acc(acc);
 
         // ---- main loop: K-tile t is in buffer t&1 (tile 0 was issued before we got here) ----
         for (int t = 0; t < nt; ++t) {
@@ -692,12 +707,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if (w_scale != nullptr) v[e] *= a_scale * w_scale[col + e];
-        if (bias != nullptr) v[e] += bias[col + e];
-        if constexpr (ACT == SPRC_ACT_GELU) v[e] = gelu_fast(v[e]);
-        if constexpr (ACT == SPRC_ACT_QUICKGELU) v[e] = quick_gelu(v[e]);
-        if (resid != nullptr) v[e] += resid[(int64_t)row * ldr + col + e];
-        if constexpr (std::is_same<OutT, fp8_t>::value) v[e] *= out_scale;
+        // fast GELU with the exact QuickGELU, for every operand type: this kernel's own pairing (see epi_value)
+        v[e] = epi_value<ACT, true, false, OutT>(v[e], w_scale != nullptr, [&] { return a_scale * w_scale[col + e]; }, bias != nullptr, [&] { return bias[col + e]; },
+                                                 resid != nullptr, [&] { return resid[(int64_t)row * ldr + col + e]; }, out_scale);
         store_out1<OutT>(C + (int64_t)row * ldc + col + e, v[e], N, col + e);
     }
 }
@@ -728,7 +740,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // MIX (T = fp16): split-precision product.  Operand rows = K fp16 elements + p.k8 e4m3 elements; the K loop runs the fp16 K-tiles on
 // v_mfma_f32_32x32x16_f16 and then the e4m3 K-tiles on the MX-scaled MFMA (block scales 2^-9 x 2^-9) into the SAME accumulators: the
 // staging, the LDS image and the interval schedule do not know the element type (a K-tile is 128 bytes of a row either way); only the
-// fragment registers and the cluster's instruction differ -- two copies of the steady interval pair, selected at compile time.
+// fragment registers and the cluster's instruction differ: the one K-tile definition (`ktile`) is instantiated per element kind, and the K loop
+// runs the fp16 instantiation first, the MX one after it.
 template <typename T, typename OutT, int ACT, bool MAX32, bool STAMP = false, bool MIX = false>
 __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -779,14 +792,6 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     // (the same for a wave whose 128 ROWS lie at or beyond M: the lower half of a ragged last row panel)
     const bool dead = __builtin_amdgcn_readfirstlane(n0 + wc * (TN * 32)) >= kq->N || m0 + wr * (TM * 32) >= kq->M;
     f32x16 acc[TM][TN];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-    };
     uint64_t ts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // ---- K loop.  The first form of this loop (round 1 / early round 2) followed the schedule above with run-time flags: its
     // s_memtime stamps showed an NC interval taking 500-600 cycles to ISSUE 12 ds_read_b128 + 3 loads -- ~20 branches per
@@ -797,8 +802,8 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     // (stages interleaved as [A s0 | A s1 | B s0 | B s1]: a parity is a 32-KB immediate), the LDS destination of a load is
     // SGPR + immediate, and the only branches left are the group's three counted waits; the last (up to three) K-tiles run
     // the same intervals on run-time flags.  NC issue 260 cycles, cluster 520, K-tile 3160 -> 2190 cycles (2048 = MFMA only).
-    // ONE code path for both groups on purpose: per-group copies of the tail made the allocator spill 2400 registers at the
-    // merge of the accumulator tuples.
+    // ONE code path for both groups on purpose (wr is a run-time SGPR flag inside the intervals): per-group copies of the tail made the
+    // allocator spill 2400 registers at the merge of the accumulator tuples.
     // (Round 2 tried a persistent tile loop that kept the kernel parameters and both tiles' descriptors live across the epilogue: they
     // spilled SGPRs into the steady loop -- 11 v_readlane per K-tile pair -- and it lost 4-9 %.  The round-5 loop above keeps nothing live:
     // tools/kloop_stat.py on a listing shows the steady loop unchanged.  Issuing the next tile's first K-tile before the epilogue, with the
@@ -830,13 +835,6 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
         }
     }
     const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(a_base), rs_w = make_rsrc(w_base);
-    using std::integral_constant;
-    typedef integral_constant<int, 0> I0;
-    typedef integral_constant<int, 1> I1;
-    typedef integral_constant<int, 2> I2;
-    typedef integral_constant<int, 3> I3;
-
-
     constexpr uint32_t PAR_BYTES = 256 * KTB, B_BASE = 2 * PAR_BYTES;   // [A s0 | A s1 | B s0 | B s1], 32 KB each
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
     const uint32_t c0 = (uint32_t)((half ^ ((r32 >> 1) & 7)) << 4);
@@ -871,176 +869,119 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
         constexpr int q = decltype(q_)::value, j = decltype(j_)::value;
         buffer_load_lds16(q >= 2 ? rs_a : rs_w, smem + (base_q[q] + par_bytes + j * 4096), pc_off[q][j], tile * KTB);
     };
-    auto piece = [&](auto q_, uint32_t par_bytes, int tile) { load_piece(q_, I0{}, par_bytes, tile); load_piece(q_, I1{}, par_bytes, tile); };
-    // fragments of k-steps 2h, 2h+1 of the K-tile in the stage of parity PAR: compile-time parity = pure immediates
-    auto reads_c = [&](auto par_, auto h_, auto mx_) {
+    auto piece = [&](auto q_, uint32_t par_bytes, int tile) { load_piece(q_, ic<0>{}, par_bytes, tile); load_piece(q_, ic<1>{}, par_bytes, tile); };
+    // fragments of k-steps 2h, 2h+1 of the K-tile in the stage of parity PAR (compile-time: pure immediates) or, PAR < 0, at run-time offset pb
+    auto reads = [&](auto par_, uint32_t pb, auto h_, auto mx_) {
         constexpr int PAR = decltype(par_)::value, h = decltype(h_)::value;
+        constexpr uint32_t POFF = PAR < 0 ? 0u : PAR * PAR_BYTES;
+        auto at = [&](uint32_t a) { if constexpr (PAR < 0) return a + pb; else return a; };
         if constexpr (decltype(mx_)::value) {
             static_for<0, TM>([&](auto i) {
-                constexpr uint32_t off = PAR * PAR_BYTES + decltype(i)::value * 32 * KTB;
-                fa8[decltype(i)::value] = lds_pair(addr_a[2 * h] + off, addr_a[2 * h + 1] + off);
+                constexpr uint32_t off = POFF + decltype(i)::value * 32 * KTB;
+                fa8[decltype(i)::value] = lds_pair(at(addr_a[2 * h]) + off, at(addr_a[2 * h + 1]) + off);
             });
             static_for<0, TN>([&](auto i) {
-                constexpr uint32_t off = PAR * PAR_BYTES + decltype(i)::value * 32 * KTB;
-                fb8[decltype(i)::value] = lds_pair(addr_b[2 * h] + off, addr_b[2 * h + 1] + off);
+                constexpr uint32_t off = POFF + decltype(i)::value * 32 * KTB;
+                fb8[decltype(i)::value] = lds_pair(at(addr_b[2 * h]) + off, at(addr_b[2 * h + 1]) + off);
             });
             return;
         }
         static_for<0, 2>([&](auto k_) {
             constexpr int k = decltype(k_)::value;
-            static_for<0, TM>([&](auto i) { fa[k][i] = lds_read128<PAR * PAR_BYTES + decltype(i)::value * 32 * KTB>(addr_a[2 * h + k]); });
-            static_for<0, TN>([&](auto i) { fb[k][i] = lds_read128<PAR * PAR_BYTES + decltype(i)::value * 32 * KTB>(addr_b[2 * h + k]); });
-        });
-    };
-    auto reads_r = [&](uint32_t par_bytes, auto h_, auto mx_) {       // run-time parity (the last K-tiles)
-        constexpr int h = decltype(h_)::value;
-        if constexpr (decltype(mx_)::value) {
-            static_for<0, TM>([&](auto i) {
-                constexpr uint32_t off = decltype(i)::value * 32 * KTB;
-                fa8[decltype(i)::value] = lds_pair(addr_a[2 * h] + par_bytes + off, addr_a[2 * h + 1] + par_bytes + off);
-            });
-            static_for<0, TN>([&](auto i) {
-                constexpr uint32_t off = decltype(i)::value * 32 * KTB;
-                fb8[decltype(i)::value] = lds_pair(addr_b[2 * h] + par_bytes + off, addr_b[2 * h + 1] + par_bytes + off);
-            });
-            return;
-        }
-        static_for<0, 2>([&](auto k_) {
-            constexpr int k = decltype(k_)::value;
-            const uint32_t an = addr_a[2 * h + k] + par_bytes, bn = addr_b[2 * h + k] + par_bytes;
-            static_for<0, TM>([&](auto i) { fa[k][i] = lds_read128<decltype(i)::value * 32 * KTB>(an); });
-            static_for<0, TN>([&](auto i) { fb[k][i] = lds_read128<decltype(i)::value * 32 * KTB>(bn); });
+            const uint32_t an = at(addr_a[2 * h + k]), bn = at(addr_b[2 * h + k]);
+            static_for<0, TM>([&](auto i) { fa[k][i] = lds_read128<POFF + decltype(i)::value * 32 * KTB>(an); });
+            static_for<0, TN>([&](auto i) { fb[k][i] = lds_read128<POFF + decltype(i)::value * 32 * KTB>(bn); });
         });
     };
     // 16 MFMAs (k-steps 2h, 2h+1 of the 128 x 64 wave tile; 8 on MX K-tiles); the second load of piece q goes out after MFMA 1
-    // (MX: MFMA 0, the same point in the cluster) (`ld`: a compile-time true in the steady state, a run-time flag in the last K-tiles)
-    auto cluster = [&](auto q_, uint32_t par_bytes, auto ld, int tile, auto mx_) {
+    // (MX: MFMA 0, the same point in the cluster) (`ld`: a compile-time true in the steady state, a run-time flag in the last K-tiles).
+    // A dead wave's cluster is that load alone.
+    auto cluster = [&](auto q_, uint32_t par_bytes, auto ld, int tile, auto mx_, auto live_) {
+        if constexpr (!decltype(live_)::value) { if (ld) load_piece(q_, ic<1>{}, par_bytes, tile); return; }
         __builtin_amdgcn_s_setprio(1);
         if constexpr (decltype(mx_)::value) {
             static_for<0, 8>([&](auto x_) {
                 constexpr int x = decltype(x_)::value, mi = x >> 1, ni = x & 1;
                 acc[mi][ni] = mfma_mx8(fb8[ni], fa8[mi], acc[mi][ni], MXSC);
-                if constexpr (x == 0) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
+                if constexpr (x == 0) { if (ld) load_piece(q_, ic<1>{}, par_bytes, tile); }
             });
         } else {
             static_for<0, 16>([&](auto x_) {
                 constexpr int x = decltype(x_)::value, k = x >> 3, mi = (x >> 1) & 3, ni = x & 1;
                 acc[mi][ni] = mfma_frag<T>(fb[k][ni], fa[k][mi], acc[mi][ni]);
-                if constexpr (x == 1) { if (ld) load_piece(q_, I1{}, par_bytes, tile); }
+                if constexpr (x == 1) { if (ld) load_piece(q_, ic<1>{}, par_bytes, tile); }
             });
         }
         __builtin_amdgcn_s_setprio(0);
     };
-    auto stamp = [&](auto i_, int t) {
-        if constexpr (STAMP) {
-            if (t == 8 && ((kq->ksplit >> decltype(i_)::value) & 1)) ts[decltype(i_)::value] = __builtin_amdgcn_s_memtime();   // ksplit = stamp mask here
+    // NC(t,1) stages K-tile t+1 (G0) or t+2 (G1): stage parity of that piece pair, indexed by the parity of t.  (Hoisted for the steady state:
+    // `wr ? pb : pn` inside the loop costs 4 s_add + a branch per K-tile pair.)
+    const uint32_t p2_bytes[2] = {wr ? 0u : PAR_BYTES, wr ? PAR_BYTES : 0u};
+    // ONE K-tile = the four barrier intervals of the schedule above, written once for every wave and every K-tile:
+    //   par_   0 | 1: the parity of t at compile time (fragment offsets are pure immediates);  < 0: run-time parity, pb added to the address registers
+    //   n1 n2  K-tiles t+1 / t+2 exist.  std::true_type in the steady state (the tests and the vmcnt(0) arms fold away: no branch is left but the
+    //          group's three counted waits), run-time bools in the last (up to three) K-tiles
+    //   live_  false_type: a DEAD wave -- its loads in the same order (the counted waits count the same loads), its waits, every barrier; no
+    //          fragment reads, no lgkmcnt wait, and of a cluster only the in-cluster load.  (st: s_memtime stamps of the STAMP build, K-tile 8)
+    auto ktile = [&](auto par_, int t, auto n1, auto n2, auto mx_, auto live_) {
+        constexpr int PAR = decltype(par_)::value;
+        constexpr bool LIVE = decltype(live_)::value;
+        const uint32_t pb = PAR < 0 ? (uint32_t)(t & 1) * PAR_BYTES : (uint32_t)PAR * PAR_BYTES, pn = pb ^ PAR_BYTES;
+        uint32_t p2;
+        if constexpr (PAR < 0) p2 = wr ? pb : pn;
+        else p2 = p2_bytes[PAR];
+        const int t_p2 = t + 1 + wr;
+        const bool has_p2 = wr ? (bool)n2 : (bool)n1;
+        auto st = [&](auto i_) {
+            if constexpr (STAMP && PAR >= 0 && LIVE) {
+                if (t == 8 && ((kq->ksplit >> decltype(i_)::value) & 1)) ts[decltype(i_)::value] = __builtin_amdgcn_s_memtime();   // ksplit = stamp mask here
+            }
+        };
+        st(ic<0>{});
+        if constexpr (LIVE) reads(par_, pb, ic<0>{}, mx_);     // NC(t,0)
+        if (n1) { piece(ic<0>{}, pn, t + 1); load_piece(ic<1>{}, ic<0>{}, pn, t + 1); }
+        st(ic<1>{});
+        if constexpr (LIVE) wait_lgkmcnt<0>();
+        if (wr == 0) { if (n1) wait_vmcnt<3>(); else wait_vmcnt<0>(); }     // A2 A3 of t landed (G1 reads them in the next interval)
+        st(ic<2>{}); barrier(); st(ic<3>{});
+        cluster(ic<1>{}, pn, n1, t + 1, mx_, live_);           // C(t,0)
+        st(ic<4>{}); barrier(); st(ic<5>{});
+        if constexpr (LIVE) reads(par_, pb, ic<1>{}, mx_);     // NC(t,1)
+        if (has_p2) { piece(ic<2>{}, p2, t_p2); load_piece(ic<3>{}, ic<0>{}, p2, t_p2); }
+        st(ic<6>{});
+        if constexpr (LIVE) wait_lgkmcnt<0>();
+        if (wr == 1) { if (n2) wait_vmcnt<3>(); else wait_vmcnt<0>(); }     // A0 A1 B2 B3 of t+1 landed; A0 A1 of t+2 may fly
+        st(ic<7>{}); barrier(); st(ic<8>{});
+        cluster(ic<3>{}, p2, has_p2, t_p2, mx_, live_);        // C(t,1)
+        st(ic<9>{});
+        if (wr == 0) { if (n1) wait_vmcnt<4>(); else wait_vmcnt<0>(); }     // B0 B1 of t+1 landed; A2 A3 of t+1 may fly
+        st(ic<10>{}); barrier(); st(ic<11>{});
+    };
+    // The K loop (two copies in the ISA, live and dead, one branch per tile): the steady state unrolled by two K-tiles, then the run-time tail.
+    auto kloop = [&](auto live_) {
+        const std::true_type yes{};
+        int t = 0;
+        // MIX: the fp16 K-tiles (nt16 even; >= 4 e4m3 K-tiles follow, so t + 3 < nt holds throughout).  A dead wave does not care about the element kind.
+        if constexpr (MIX && decltype(live_)::value) {
+            for (; t + 1 < nt16; t += 2) {
+                ktile(ic<0>{}, t, yes, yes, std::false_type{}, live_);
+                ktile(ic<1>{}, t + 1, yes, yes, std::false_type{}, live_);
+            }
         }
-    };
-    // NC(t,1) stages K-tile t+1 (G0) or t+2 (G1): tile index and stage parity of that piece pair
-    const uint32_t p2_bytes[2] = {wr ? 0u : PAR_BYTES, wr ? PAR_BYTES : 0u};      // indexed by the parity of t
-    // steady state: K-tiles t+1 and t+2 exist, parity of t known at compile time -> no branch but the group's waits
-    auto steady = [&](auto par_, int t, auto mx_) {
-        constexpr int PAR = decltype(par_)::value;
-        constexpr uint32_t pn = (PAR ^ 1) * PAR_BYTES;
-        const uint32_t p2 = p2_bytes[PAR];
-        const int t_p2 = t + 1 + wr;
-        stamp(integral_constant<int, 0>{}, t);
-        reads_c(par_, I0{}, mx_);                           // NC(t,0)
-        piece(I0{}, pn, t + 1);
-        load_piece(I1{}, I0{}, pn, t + 1);
-        stamp(integral_constant<int, 1>{}, t);
-        wait_lgkmcnt<0>();
-        if (wr == 0) wait_vmcnt<3>();                       // A2 A3 of t landed (G1 reads them in the next interval)
-        stamp(integral_constant<int, 2>{}, t);
-        barrier();
-        stamp(integral_constant<int, 3>{}, t);
-        cluster(I1{}, pn, std::true_type{}, t + 1, mx_);    // C(t,0)
-        stamp(integral_constant<int, 4>{}, t);
-        barrier();
-        stamp(integral_constant<int, 5>{}, t);
-        reads_c(par_, I1{}, mx_);                           // NC(t,1)
-        piece(I2{}, p2, t_p2);
-        load_piece(I3{}, I0{}, p2, t_p2);
-        stamp(integral_constant<int, 6>{}, t);
-        wait_lgkmcnt<0>();
-        if (wr == 1) wait_vmcnt<3>();                       // A0 A1 B2 B3 of t+1 landed; A0 A1 of t+2 may fly
-        stamp(integral_constant<int, 7>{}, t);
-        barrier();
-        stamp(integral_constant<int, 8>{}, t);
-        cluster(I3{}, p2, std::true_type{}, t_p2, mx_);     // C(t,1)
-        stamp(integral_constant<int, 9>{}, t);
-        if (wr == 0) wait_vmcnt<4>();                       // B0 B1 of t+1 landed; A2 A3 of t+1 may fly
-        stamp(integral_constant<int, 10>{}, t);
-        barrier();
-        stamp(integral_constant<int, 11>{}, t);
-    };
-    // the last (up to three) K-tiles: the same interval structure on run-time flags
-    auto tail = [&](int t, bool n1, bool n2, auto mx_) {
-        const uint32_t pb = (uint32_t)(t & 1) * PAR_BYTES, pn = pb ^ PAR_BYTES;
-        const uint32_t p2 = wr ? pb : pn;
-        const int t_p2 = t + 1 + wr;
-        const bool has_p2 = wr ? n2 : n1;
-        reads_r(pb, I0{}, mx_);                             // NC(t,0)
-        if (n1) { piece(I0{}, pn, t + 1); load_piece(I1{}, I0{}, pn, t + 1); }
-        wait_lgkmcnt<0>();
-        if (wr == 0) { if (n1) wait_vmcnt<3>(); else wait_vmcnt<0>(); }
-        barrier();
-        cluster(I1{}, pn, n1, t + 1, mx_);                  // C(t,0)
-        barrier();
-        reads_r(pb, I1{}, mx_);                             // NC(t,1)
-        if (has_p2) { piece(I2{}, p2, t_p2); load_piece(I3{}, I0{}, p2, t_p2); }
-        wait_lgkmcnt<0>();
-        if (wr == 1) { if (n2) wait_vmcnt<3>(); else wait_vmcnt<0>(); }
-        barrier();
-        cluster(I3{}, p2, has_p2, t_p2, mx_);               // C(t,1)
-        if (wr == 0) { if (n1) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-        barrier();
-    };
-    // the same intervals for a DEAD wave: its loads in the same order (the counted waits count the same loads), its waits, every barrier
-    auto steady_dead = [&](auto par_, int t) {
-        constexpr int PAR = decltype(par_)::value;
-        constexpr uint32_t pn = (PAR ^ 1) * PAR_BYTES;
-        const uint32_t p2 = p2_bytes[PAR];
-        const int t_p2 = t + 1 + wr;
-        piece(I0{}, pn, t + 1);                             // NC(t,0)
-        load_piece(I1{}, I0{}, pn, t + 1);
-        if (wr == 0) wait_vmcnt<3>();
-        barrier();
-        load_piece(I1{}, I1{}, pn, t + 1);                  // C(t,0): the in-cluster load
-        barrier();
-        piece(I2{}, p2, t_p2);                              // NC(t,1)
-        load_piece(I3{}, I0{}, p2, t_p2);
-        if (wr == 1) wait_vmcnt<3>();
-        barrier();
-        load_piece(I3{}, I1{}, p2, t_p2);                   // C(t,1)
-        if (wr == 0) wait_vmcnt<4>();
-        barrier();
-    };
-    auto tail_dead = [&](int t, bool n1, bool n2) {
-        const uint32_t pb = (uint32_t)(t & 1) * PAR_BYTES, pn = pb ^ PAR_BYTES;
-        const uint32_t p2 = wr ? pb : pn;
-        const int t_p2 = t + 1 + wr;
-        const bool has_p2 = wr ? n2 : n1;
-        if (n1) { piece(I0{}, pn, t + 1); load_piece(I1{}, I0{}, pn, t + 1); }
-        if (wr == 0) { if (n1) wait_vmcnt<3>(); else wait_vmcnt<0>(); }
-        barrier();
-        if (n1) load_piece(I1{}, I1{}, pn, t + 1);
-        barrier();
-        if (has_p2) { piece(I2{}, p2, t_p2); load_piece(I3{}, I0{}, p2, t_p2); }
-        if (wr == 1) { if (n2) wait_vmcnt<3>(); else wait_vmcnt<0>(); }
-        barrier();
-        if (has_p2) load_piece(I3{}, I1{}, p2, t_p2);
-        if (wr == 0) { if (n1) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-        barrier();
+        for (; t + 3 < nt; t += 2) {
+            ktile(ic<0>{}, t, yes, yes, MXL{}, live_);
+            ktile(ic<1>{}, t + 1, yes, yes, MXL{}, live_);
+        }
+        for (; t < nt; ++t) ktile(ic<-1>{}, t, t + 1 < nt, t + 2 < nt, MXL{}, live_);
     };
     // prologue: K-tile 0 resident for everyone (each group stages its four pieces), G1's early pieces of K-tile 1 in
     // flight, G1 one interval behind
     if constexpr (STAMP) pro_ts[0] = __builtin_amdgcn_s_memtime();
     static_for<0, 4>([&](auto q_) { piece(q_, 0u, 0); });
     if constexpr (STAMP) pro_ts[1] = __builtin_amdgcn_s_memtime();
-    if (wr == 1 && nt > 1) { piece(I2{}, PAR_BYTES, 1); piece(I3{}, PAR_BYTES, 1); }
+    if (wr == 1 && nt > 1) { piece(ic<2>{}, PAR_BYTES, 1); piece(ic<3>{}, PAR_BYTES, 1); }
     asm volatile("" ::: "memory");
-    zero_acc();                                         // 128 v_mov under the first loads' latency
+    zero_acc(acc);                                      // 128 v_mov under the first loads' latency
     asm volatile("" ::: "memory");
     if (wr == 1 && nt > 1) wait_vmcnt<4>();
     else wait_vmcnt<0>();
@@ -1048,27 +989,8 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     barrier();
     if (wr == 1) barrier();
     if constexpr (STAMP) tile_ts[1] = __builtin_amdgcn_s_memtime();
-    if (dead) {
-        int t = 0;
-        for (; t + 3 < nt; t += 2) {
-            steady_dead(I0{}, t);
-            steady_dead(I1{}, t + 1);
-        }
-        for (; t < nt; ++t) tail_dead(t, t + 1 < nt, t + 2 < nt);
-    } else {
-        int t = 0;
-        if constexpr (MIX) {                                // fp16 K-tiles (nt16 even; >= 4 e4m3 K-tiles follow, so t + 3 < nt holds throughout)
-            for (; t + 1 < nt16; t += 2) {
-                steady(I0{}, t, std::false_type{});
-                steady(I1{}, t + 1, std::false_type{});
-            }
-        }
-        for (; t + 3 < nt; t += 2) {
-            steady(I0{}, t, MXL{});
-            steady(I1{}, t + 1, MXL{});
-        }
-        for (; t < nt; ++t) tail(t, t + 1 < nt, t + 2 < nt, MXL{});
-    }
+    if (dead) kloop(std::false_type{});
+    else kloop(std::true_type{});
     if (wr == 0) barrier();                                 // G1 spent its extra barrier up front
     if constexpr (STAMP) tile_ts[2] = __builtin_amdgcn_s_memtime();
     // The epilogue reads ITS parameters (output / residual / bias pointers, leading dimensions, the row map, scales) through the laundered
@@ -1077,8 +999,7 @@ __global__ __launch_bounds__(512) void gemm_anti_kernel(GemmParams p) {
     // steady state (seen: 16 per K-tile pair, the whole step 90.8 -> 93.9 ms, after an epilogue change added a handful of uniform values).
     GemmParams pe = *(const GemmParams*)kernarg_params();
     if (second) { pe.bias = pe.bias2; pe.c_off = pe.c_off2; }
-    const bool vec_ok = (pe.N % 4 == 0) && (pe.ldc % 4 == 0) && (pe.resid == nullptr || pe.ldr % 4 == 0) &&
-                        ((uintptr_t)pe.C % (4 * sizeof(OutT)) == 0) && ((uintptr_t)pe.bias % 16 == 0) && ((uintptr_t)pe.resid % 16 == 0);
+    const bool vec_ok = epi_vec_ok<OutT>(pe);       // (ahead of the dead test: evaluated in the call, hipcc spills 2-3 more SGPRs in the epilogue)
     if (!dead || MAX32) gemm_epilogue<T, OutT, ACT, MAX32, TM, TN>(pe, acc, m0, n0, wr, wc, r32, half, vec_ok, smem, wave);
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the epilogue's stores have left the wave
