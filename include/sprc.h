@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SPRC_ABI_VERSION 6
+#define SPRC_ABI_VERSION 7
 
 enum { SPRC_OK = 0, SPRC_EINVAL = -1, SPRC_ELAUNCH = -2, SPRC_EWORKSPACE = -3, SPRC_EUNSUPPORTED = -4 };
 enum { SPRC_F32 = 0, SPRC_BF16 = 1,
@@ -257,6 +257,23 @@ int sprc_topk(const float* sim, int64_t ld, const int32_t* gidx, int32_t idx_bas
  * of gallery item t in the stable order, without sorting (exact Recall@K for any K). */
 int sprc_rank_of(const float* sim, int64_t ld, const int32_t* listed, int32_t nq, int32_t N, int32_t L,
                  int32_t* rank, sprc_stream s);
+
+/* Average precision at K with several ground truths per query (ABI 7): the metric of the CIRCO benchmark.  The reference
+ * ships the CIRCO dataset class (data_utils.py:289-426) but no evaluator, so there is no call site to cite; the metric
+ * is the dataset's published protocol, stated on the ranking contract above.  For query q let r_1 .. r_G' be the
+ * 0-based positions, in the stable order of row q, of the G' ground truths gt[q,:] that are not padding.  Then
+ *     ap[q,k] = ( SUM over i with r_i < K  of  (1 + #{ j : r_j < r_i }) / (r_i + 1) )  /  min(G', K),     K = ks[k]
+ * in fp64, the terms added in ascending order of r_i (a fixed order: the result is reproducible bit for bit);
+ * G' = 0 gives 0.  No gallery item is removed from the order (the reference image stays, as on the FashionIQ path,
+ * validate_blip.py:49-51).
+ *   gt    DEVICE int32 [nq,G], 1 <= G <= 32; entries < 0 or >= N are padding.  Two equal entries in one row are
+ *         UNDEFINED (the ranks would not be distinct): callers remove duplicates first.
+ *   ks    HOST int32 [nk], 1 <= nk <= 8, every K >= 1 (read before the call returns).
+ *   ap    DEVICE double [nq,nk].
+ *   rank  DEVICE int32 [nq,G] or NULL: rank[q,i] as sprc_rank_of gives it, -1 for padding.
+ * One pass over the row serves all G ground truths. */
+int sprc_ap_at_k(const float* sim, int64_t ld, const int32_t* gt, int32_t nq, int32_t N, int32_t G,
+                 const int32_t* ks, int32_t nk, double* ap, int32_t* rank, sprc_stream s);
 
 /* ------------------------------------------------------------------------------------------
  * Composite forward passes (one call per batch; the kernels above, sequenced on `s`)

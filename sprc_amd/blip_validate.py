@@ -2,7 +2,9 @@
 """`python -m sprc_amd.blip_validate --dataset CIRR --blip-model-name blip2_cir_align_prompt --model-path X`
 
 Entry point with the reference's flags and printed JSON keys (src/blip_validate.py:103-155), running the
-retrieval path on the MI355X HIP engine.  Extra flag: --dtype (bf16 | fp32).
+retrieval path on the MI355X HIP engine.  Extra flag: --dtype (bf16 | fp32).  `--dataset CIRCO [--circo-path P]` has no
+counterpart in the reference's script (it ships the CIRCO dataset class without an evaluator): mAP@K and Recall@K for
+K in {5, 10, 25, 50} on the val split.
 """
 from __future__ import annotations
 
@@ -14,7 +16,8 @@ from statistics import geometric_mean, harmonic_mean, mean
 
 import torch
 
-from .harness import compute_cirr_val_metrics, compute_fiq_val_metrics, extract_index_blip_features
+from .harness import (circo_reference_ids, compute_circo_val_metrics, compute_cirr_val_metrics, compute_fiq_val_metrics,
+                      extract_index_blip_features)
 from .index import load_index, save_index
 from .model import load_model_and_preprocess
 
@@ -60,22 +63,31 @@ def _raw_store_dtype(model) -> torch.dtype:
     return torch.bfloat16 if eng.dt == L.SPRC_BF16 else torch.float32
 
 
-def _gallery(dataset, model, cache, tag, backbone, dtype, num_workers: int = 2):
+def _gallery(dataset, model, cache, tag, backbone, dtype, num_workers: int = 2, keep_raw=True):
     """Encoded gallery `((feats, raw), names)`: from the feature store `<cache>/<tag>-...-<checkpoint fingerprint>.safetensors`
     when it exists AND was written by this checkpoint, else encoded now (and stored when a cache directory was given).
-    No reference counterpart: utils.py:46-77 re-encodes on every run."""
+    No reference counterpart: utils.py:46-77 re-encodes on every run.
+    keep_raw=<names>: raw embeddings are kept, and stored, for these images only (harness.RawStore)."""
     if not cache:
-        return extract_index_blip_features(dataset, model, num_workers=num_workers)
+        return extract_index_blip_features(dataset, model, num_workers=num_workers, keep_raw=keep_raw)
     fp = model_fingerprint(model)
     path = os.path.join(cache, f"{tag}-{backbone}-{dtype}-{fp[:16]}.safetensors")
     if os.path.exists(path):
         (feats, raw), names, meta = load_index(path, device=model.device)
-        if meta.get("checkpoint_sha256") == fp:
+        row_of = {n: i for i, n in enumerate(names)}
+        covered = keep_raw is True or all(n in row_of and raw[row_of[n]] is not None for n in set(keep_raw))
+        if meta.get("checkpoint_sha256") == fp and covered:
             print(f"loaded {len(names)} gallery rows from {path} ({meta})")
             return (feats, raw), names
-        print(f"{path}: written by another checkpoint ({meta.get('checkpoint_sha256', '?')[:16]}), re-encoding")
-    (feats, raw), names = extract_index_blip_features(dataset, model, num_workers=num_workers)
-    save_index(path, feats, names, raw=raw, backbone=backbone, compute_dtype=dtype, checkpoint_sha256=fp, raw_dtype=_raw_store_dtype(model))
+        print(f"{path}: " + (f"written by another checkpoint ({meta.get('checkpoint_sha256', '?')[:16]})" if covered else
+                             "lacks the raw embeddings of some reference images") + ", re-encoding")
+    (feats, raw), names = extract_index_blip_features(dataset, model, num_workers=num_workers, keep_raw=keep_raw)
+    if keep_raw is True:
+        save_index(path, feats, names, raw=raw, backbone=backbone, compute_dtype=dtype, checkpoint_sha256=fp, raw_dtype=_raw_store_dtype(model))
+    else:
+        kept = sorted(raw.rows)
+        save_index(path, feats, names, raw=torch.stack([raw.rows[i] for i in kept]), raw_names=[names[i] for i in kept], backbone=backbone,
+                   compute_dtype=dtype, checkpoint_sha256=fp, raw_dtype=_raw_store_dtype(model))
     return (feats, raw), names
 
 
@@ -177,9 +189,33 @@ def blip_validate_fiq(val_dress_types, blip_model_name, backbone, model_path, dt
 clip_finetune_fiq = blip_validate_fiq      # the reference's (misleading) name
 
 
+def blip_validate_circo(blip_model_name, backbone, blip_model_path, dtype="fp16", index_cache=None, gpu_preprocess=False,
+                        vit_depth=None, reuse_reference_kv=False, circo_path=None):
+    """CIRCO val: mAP@K and Recall@K for K in {5, 10, 25, 50} (harness.compute_circo_val_metrics; no reference counterpart).
+    Raw ViT embeddings are kept for the queries' reference images only: the gallery has 123 403 images."""
+    from .data_utils import CIRCODataset, base_path
+    model, txt = _load(blip_model_name, backbone, blip_model_path, dtype, vit_depth)
+    preprocess, workers = _preprocess(gpu_preprocess, model.device)
+    root = circo_path or base_path / "CIRCO"
+    relative_val = CIRCODataset(root, "val", "relative", preprocess)
+    classic = CIRCODataset(root, "val", "classic", preprocess)
+    if _sharded():
+        _warn_index_cache_ignored(index_cache)
+        from .dist_eval import compute_circo_val_metrics_sharded
+        out = compute_circo_val_metrics_sharded(relative_val, classic, model, txt, num_workers=workers)
+    else:
+        feats, names = _gallery(classic, model, index_cache, "circo-val", backbone, dtype, workers,
+                                keep_raw=circo_reference_ids(relative_val))
+        out = compute_circo_val_metrics(relative_val, model, feats, names, txt, reuse_reference_kv=reuse_reference_kv and dtype != "fp32")
+    if _rank0():
+        print(json.dumps(out, indent=4))
+    return out
+
+
 def main(argv=None):
     p = ArgumentParser()
-    p.add_argument("--dataset", type=str, required=True, help="should be either 'CIRR' or 'fashionIQ'")
+    p.add_argument("--dataset", type=str, required=True, help="should be 'CIRR', 'fashionIQ' or 'CIRCO'")
+    p.add_argument("--circo-path", type=str, default=None, help="CIRCO: the dataset directory (default: <data root>/CIRCO)")
     p.add_argument("--blip-model-name", default="blip2_cir_align_prompt", type=str)
     p.add_argument("--backbone", type=str, default="pretrain", help="pretrain for vit-g, pretrain_vitL for vit-l")
     p.add_argument("--model-path", type=str)
@@ -187,12 +223,15 @@ def main(argv=None):
                    help="fp16 (default): the reference's GPU numerics -- fp16 ViT, Q-Former at ~fp32 product precision")
     p.add_argument("--index-cache", default=None, help="directory of gallery feature stores (sprc_amd/index.py): encode once, reuse")
     p.add_argument("--gpu-preprocess", action="store_true", help="pad / bicubic resize / crop / normalise on the GPU (bit-identical to the PIL transform)")
-    p.add_argument("--reuse-reference-kv", action="store_true", help="CIRR: project each distinct reference image to the Q-Former's cross-attention "
+    p.add_argument("--reuse-reference-kv", action="store_true", help="CIRR / CIRCO: project each distinct reference image to the Q-Former's cross-attention "
                    "K|V once instead of once per query (same scores; single-process, 16-bit engines)")
     p.add_argument("--vit-depth", type=int, default=None, help="truncate the ViT to N blocks (entry-point smoke tests only)")
     a = p.parse_args(argv)
-    if a.dataset.lower() not in ("fashioniq", "cirr"):
-        raise ValueError("Dataset should be either 'CIRR' or 'FashionIQ")
+    if a.dataset.lower() not in ("fashioniq", "cirr", "circo"):
+        raise ValueError("Dataset should be 'CIRR', 'FashionIQ' or 'CIRCO'")
+    if a.dataset.lower() == "circo":
+        return blip_validate_circo(a.blip_model_name, a.backbone, a.model_path, a.dtype, a.index_cache, a.gpu_preprocess, a.vit_depth,
+                                   reuse_reference_kv=a.reuse_reference_kv, circo_path=a.circo_path)
     if a.dataset.lower() == "cirr":
         return blip_validate_cirr(a.blip_model_name, a.backbone, a.model_path, a.dtype, a.index_cache, a.gpu_preprocess, a.vit_depth,
                                   reuse_reference_kv=a.reuse_reference_kv)

@@ -13,6 +13,8 @@
 // exchange stages on shuffles) and bitonic-merges it into its sorted running top-64 held one key
 // per lane.  The 4 per-wave lists are merged through LDS.  HBM traffic = the sim row once.
 // sprc_rank_of: position of listed gallery items in that order by counting smaller keys (no sort).
+// sprc_ap_at_k: average precision at K over up to 32 ground truths per query (the CIRCO protocol): the ranks of all ground
+// truths from ONE counting pass over the row, then AP@K in fp64 from those ranks, summed in ascending-rank order.
 #include "common.hpp"
 
 namespace sprc {
@@ -160,6 +162,75 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const float* __restrict__ 
     }
 }
 
+constexpr int AP_MAX_G = 32, AP_MAX_K = 8;
+struct ApKs {
+    int32_t k[AP_MAX_K];           // the K values, by value: the ABI takes them from HOST memory
+};
+
+// One workgroup per query.  The keys of the query's ground truths sit in LDS; every thread walks the row with stride 256
+// (coalesced) and counts, for each of the GP ground-truth slots at once, the keys smaller than that slot's -- GP counters in
+// registers, the row read once.  Wave sums by shuffle, the four waves meet in LDS (integer adds: order-free).  Wave 0 then
+// places the ranks in ascending order (a ground truth's place among the ground truths is its own count of smaller ranks)
+// and lane k sums the fp64 terms of ks.k[k] in that order.
+template <int GP>
+__global__ __launch_bounds__(256) void ap_at_k_kernel(const float* __restrict__ sim, int64_t ld, const int32_t* __restrict__ gt, int N,
+                                                      int G, ApKs ks, int nk, double* __restrict__ ap, int32_t* __restrict__ rank) {
+    __shared__ uint64_t s_t[GP];
+    __shared__ int s_cnt[GP];
+    __shared__ int s_sorted[AP_MAX_G];
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const float* row = sim + q * ld;
+    if (tid < GP) {
+        const int t = tid < G ? gt[q * G + tid] : -1;
+        // padding gets key 0: no key of the row is smaller (a valid key has a non-zero high word), its count stays 0
+        s_t[tid] = (t >= 0 && t < N) ? (((uint64_t)dist_bits(row[t]) << 32) | (uint32_t)t) : 0ull;
+        s_cnt[tid] = 0;
+    }
+    if (tid < AP_MAX_G) s_sorted[tid] = 0x7fffffff;
+    __syncthreads();
+    int cnt[GP];
+#pragma unroll
+    for (int l = 0; l < GP; ++l) cnt[l] = 0;
+    for (int n = tid; n < N; n += 256) {
+        const uint64_t key = ((uint64_t)dist_bits(row[n]) << 32) | (uint32_t)n;
+#pragma unroll
+        for (int l = 0; l < GP; ++l) cnt[l] += (key < s_t[l]) ? 1 : 0;
+    }
+#pragma unroll
+    for (int l = 0; l < GP; ++l) {
+        int v = cnt[l];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if ((tid & 63) == 0) atomicAdd(&s_cnt[l], v);
+    }
+    __syncthreads();
+    int n_gt = 0;                                  // ground truths of this query that are not padding
+    if (tid < GP) {
+        const bool valid = s_t[tid] != 0ull;
+        const int r = valid ? s_cnt[tid] : -1;
+        if (rank && tid < G) rank[q * G + tid] = r;
+        int before = 0;                            // ground truths ranked before this one
+        for (int j = 0; j < GP; ++j) {
+            const bool vj = s_t[j] != 0ull;
+            n_gt += vj ? 1 : 0;
+            before += (vj && valid && s_cnt[j] < r) ? 1 : 0;
+        }
+        if (valid) s_sorted[before] = r;           // ranks are distinct (the index is part of the key): a permutation
+    }
+    __syncthreads();
+    if (tid < nk) {
+        const int K = ks.k[tid];
+        double acc = 0.0;
+        for (int i = 0; i < n_gt; ++i) {
+            const int ri = s_sorted[i];
+            if (ri < K) acc += (double)(i + 1) / (double)(ri + 1);
+        }
+        const int denom = n_gt < K ? n_gt : K;
+        ap[q * nk + tid] = denom > 0 ? acc / (double)denom : 0.0;
+    }
+}
+
 }  // namespace sprc
 
 using namespace sprc;
@@ -182,5 +253,29 @@ extern "C" int sprc_rank_of(const float* sim, int64_t ld, const int32_t* listed,
     ProfScope prof(SPRC_K_RANK, (hipStream_t)s, 0.0, (double)nq * N * 4.0);
     hipLaunchKernelGGL(rank_of_kernel, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, listed, N, L, rank);
     SPRC_CHECK_LAUNCH("sprc_rank_of");
+    return SPRC_OK;
+}
+
+extern "C" int sprc_ap_at_k(const float* sim, int64_t ld, const int32_t* gt, int32_t nq, int32_t N, int32_t G, const int32_t* ks,
+                            int32_t nk, double* ap, int32_t* rank, sprc_stream s) {
+    SPRC_REQUIRE(sim && gt && ks && ap, "sprc_ap_at_k: null pointer");
+    SPRC_REQUIRE(nq > 0 && N > 0 && ld >= N, "sprc_ap_at_k: bad shape nq=%d N=%d ld=%lld", nq, N, (long long)ld);
+    SPRC_REQUIRE(G >= 1 && G <= AP_MAX_G, "sprc_ap_at_k: G=%d must be in [1,%d]", G, AP_MAX_G);
+    SPRC_REQUIRE(nk >= 1 && nk <= AP_MAX_K, "sprc_ap_at_k: nk=%d must be in [1,%d]", nk, AP_MAX_K);
+    ApKs kk = {};
+    for (int i = 0; i < nk; ++i) {
+        SPRC_REQUIRE(ks[i] >= 1, "sprc_ap_at_k: ks[%d]=%d must be >= 1", i, ks[i]);
+        kk.k[i] = ks[i];
+    }
+    ProfScope prof(SPRC_K_RANK, (hipStream_t)s, 0.0, (double)nq * N * 4.0);
+    if (G <= 8)
+        hipLaunchKernelGGL(ap_at_k_kernel<8>, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gt, N, G, kk, nk, ap, rank);
+    else if (G <= 16)
+        hipLaunchKernelGGL(ap_at_k_kernel<16>, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gt, N, G, kk, nk, ap, rank);
+    else if (G <= 24)
+        hipLaunchKernelGGL(ap_at_k_kernel<24>, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gt, N, G, kk, nk, ap, rank);
+    else
+        hipLaunchKernelGGL(ap_at_k_kernel<32>, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gt, N, G, kk, nk, ap, rank);
+    SPRC_CHECK_LAUNCH("sprc_ap_at_k");
     return SPRC_OK;
 }

@@ -1,8 +1,8 @@
 """Host-side datasets and preprocessing for the evaluation entry points (image decode is host I/O; SURVEY.md
 section 8(f) N3 keeps GPU preprocessing as a "next" row).
 
-Same on-disk layout, dataset modes and item tuples as the reference's src/data_utils.py (CIRR :203-286,
-FashionIQ :108-200, TargetPad + CLIP normalisation :49-105) so the reference's data directory works as is;
+Same on-disk layout, dataset modes and items as the reference's src/data_utils.py (CIRR :203-286,
+FashionIQ :108-200, CIRCO :289-426, TargetPad + CLIP normalisation :49-105) so the reference's data directory works as is;
 the root is `SPRC_DATA_ROOT` (default: the parent of this repository, like the reference's `base_path`).
 torchvision is not required: the transform is PIL + torch.
 """
@@ -11,7 +11,7 @@ from __future__ import annotations
 import json
 import os
 from pathlib import Path
-from typing import Callable, List
+from typing import Callable, Dict, List, Union
 
 import numpy as np
 import torch
@@ -145,6 +145,10 @@ def targetpad_transform_gpu(target_ratio: float, dim: int, device="cuda") -> Cal
 
 
 class _Base(Dataset):
+    """A dataset keeps the directory it was built over (`self.root`): its items are produced in loader workers, and a worker
+    started from a fork server imports this module under the SERVER's environment -- `base_path` there is whatever
+    SPRC_DATA_ROOT was when the first loader of the process started, not what it is now."""
+
     def __getitem__(self, index):
         try:
             return self._get(index)
@@ -163,7 +167,8 @@ class CIRRDataset(_Base):
         if mode not in ("relative", "classic"):
             raise ValueError("mode should be in ['relative', 'classic']")
         self.split, self.mode, self.preprocess = split, mode, preprocess
-        root = base_path / "cirr_dataset" / "cirr"
+        self.root = base_path / "cirr_dataset"
+        root = self.root / "cirr"
         self.triplets = json.loads((root / "captions" / f"cap.rc2.{split}.json").read_text())
         self.name_to_relpath = json.loads((root / "image_splits" / f"split.rc2.{split}.json").read_text())
         self.names = list(self.name_to_relpath.keys())
@@ -171,7 +176,7 @@ class CIRRDataset(_Base):
 
     def _image(self, name):
         from PIL import Image
-        return self.preprocess(Image.open(base_path / "cirr_dataset" / self.name_to_relpath[name]))
+        return self.preprocess(Image.open(self.root / self.name_to_relpath[name]))
 
     def _get(self, index):
         if self.mode == "classic":
@@ -201,7 +206,7 @@ class FashionIQDataset(_Base):
             if d not in ("dress", "shirt", "toptee"):
                 raise ValueError("dress_type should be in ['dress', 'shirt', 'toptee']")
         self.split, self.mode, self.dress_types, self.preprocess = split, mode, dress_types, preprocess
-        root = base_path / "fashionIQ_dataset"
+        root = self.root = base_path / "fashionIQ_dataset"
         self.triplets, self.image_names = [], []
         for d in dress_types:
             self.triplets += json.loads((root / "captions" / f"cap.{d}.{split}.json").read_text())
@@ -210,7 +215,7 @@ class FashionIQDataset(_Base):
 
     def _image(self, name):
         from PIL import Image
-        return self.preprocess(Image.open(base_path / "fashionIQ_dataset" / "images" / f"{name}.png"))
+        return self.preprocess(Image.open(self.root / "images" / f"{name}.png"))
 
     def _get(self, index):
         if self.mode == "classic":
@@ -225,3 +230,64 @@ class FashionIQDataset(_Base):
 
     def __len__(self):
         return len(self.triplets) if self.mode == "relative" else len(self.image_names)
+
+
+class CIRCODataset(_Base):
+    """CIRCO over the COCO-2017 unlabeled gallery (data_utils.py:289-426).  Items are dicts, as in the reference:
+    'classic': {img, img_id}; 'relative': val -> {reference_img, reference_imd_id (the reference's spelling), target_img,
+    target_img_id, relative_caption, shared_concept, gt_img_ids (padded with '' to max_num_gts), query_id},
+    test -> the same without the target keys.  Ids are strings.  An item that cannot be produced (an unreadable file) is
+    `None`, as for the other datasets of this file: the loaders drop it (the reference's class lets the exception escape its
+    DataLoader instead, which ends a 123 403-image gallery pass at the first bad file).
+
+    Over the reference: `.names` (the gallery ids in index order, what dist_eval.gallery_names reads) and `query(index)`,
+    a relative item's metadata without its images -- an evaluation pass needs captions and ids, not 2 x 220 decoded files."""
+
+    max_num_gts = 23                     # data_utils.py:331: the longest ground-truth list of the benchmark
+
+    def __init__(self, data_path: Union[str, Path], split: str, mode: str, preprocess: Callable):
+        if mode not in ("relative", "classic"):
+            raise ValueError("mode should be in ['relative', 'classic']")
+        if split not in ("test", "val"):
+            raise ValueError("split should be in ['test', 'val']")
+        self.data_path = Path(data_path)
+        self.split, self.mode, self.preprocess = split, mode, preprocess
+        coco = self.data_path / "COCO2017_unlabeled"
+        info = json.loads((coco / "annotations" / "image_info_unlabeled2017.json").read_text())["images"]
+        self.img_paths = [coco / "unlabeled2017" / i["file_name"] for i in info]
+        self.img_ids = [i["id"] for i in info]
+        self.names = [str(i) for i in self.img_ids]
+        self.img_ids_indexes_map = {n: k for k, n in enumerate(self.names)}
+        self.annotations: List[dict] = json.loads((self.data_path / "annotations" / f"{split}.json").read_text())
+        print(f"CIRCODataset {split} dataset in {mode} mode initialized")
+
+    def get_target_img_ids(self, index) -> Dict[str, int]:
+        a = self.annotations[index]
+        return {"target_img_id": a["target_img_id"], "gt_img_ids": a["gt_img_ids"]}
+
+    def query(self, index) -> dict:
+        """The relative item `index` without its image entries."""
+        a = self.annotations[index]
+        item = {"reference_imd_id": str(a["reference_img_id"]), "relative_caption": a["relative_caption"],
+                "shared_concept": a["shared_concept"], "query_id": str(a["id"])}
+        if self.split == "val":
+            gts = [str(g) for g in a["gt_img_ids"]]
+            item.update(target_img_id=str(a["target_img_id"]), gt_img_ids=gts + [""] * (self.max_num_gts - len(gts)))
+        return item
+
+    def _image(self, img_id: str):
+        from PIL import Image
+        return self.preprocess(Image.open(self.img_paths[self.img_ids_indexes_map[img_id]]))
+
+    def _get(self, index) -> dict:
+        if self.mode == "classic":
+            name = self.names[index]
+            return {"img": self._image(name), "img_id": name}
+        item = self.query(index)
+        item["reference_img"] = self._image(item["reference_imd_id"])
+        if self.split == "val":
+            item["target_img"] = self._image(item["target_img_id"])
+        return item
+
+    def __len__(self):
+        return len(self.annotations) if self.mode == "relative" else len(self.img_ids)

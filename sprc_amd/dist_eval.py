@@ -1,5 +1,6 @@
 """Gallery-sharded evaluation: the CIRR / FashionIQ protocols of src/validate_blip.py:232-285, :24-57 and
-src/cirr_test_submission.py:61-132 with the gallery split over the ranks of one node.
+src/cirr_test_submission.py:61-132, and the CIRCO protocol of sprc_amd/harness.py (no reference counterpart), with the
+gallery split over the ranks of one node.
 
 The reference is single-process (src/utils.py:14-17); what must be preserved is its OUTPUT: the seven CIRR numbers, the
 two FashionIQ numbers per category, the two submission dicts.  Per rank (one process per GPU, `torchrun`):
@@ -75,6 +76,26 @@ def fiq_val_queries(relative_val_dataset, txt_processors) -> QuerySet:
         ref, tgt, caps = item
         q.ref_names.append(ref); q.target_names.append(tgt)
         q.captions.append(txt_processors["eval"](fiq_compose_caption(caps[0], caps[1])))
+    return q
+
+
+def circo_val_queries(relative_val_dataset, txt_processors) -> QuerySet:
+    """CIRCO val: group_members = the query's ground-truth ids (unpadded), pair_ids = the query ids."""
+    from .harness import _circo_queries
+    q = QuerySet([], [], [], [], [])
+    for item in _circo_queries(relative_val_dataset):
+        q.ref_names.append(item["reference_imd_id"]); q.target_names.append(item["target_img_id"])
+        q.group_members.append([g for g in item["gt_img_ids"] if g != ""]); q.pair_ids.append(item["query_id"])
+        q.captions.append(txt_processors["eval"](item["relative_caption"]))
+    return q
+
+
+def circo_test_queries(relative_test_dataset, txt_processors) -> QuerySet:
+    from .harness import _circo_queries
+    q = QuerySet([], [], None, None, [])
+    for item in _circo_queries(relative_test_dataset):
+        q.ref_names.append(item["reference_imd_id"]); q.pair_ids.append(item["query_id"])
+        q.captions.append(txt_processors["eval"](item["relative_caption"]))
     return q
 
 
@@ -253,6 +274,31 @@ def cirr_test_dicts_from_topk(top_idx, listed_sim, ref_idx, group_idx, pairs_id,
     return top, sub
 
 
+def circo_metrics_from_topk(top_idx, gt_idx, tgt_idx) -> Dict[str, float]:
+    """The eight CIRCO numbers of harness.circo_metrics_from_sim from the merged top-50 alone: AP@K for K <= 50 needs the
+    positions of the ground truths that fall inside the first 50, Recall@K the target's.  Host code; the terms are formed
+    and added exactly as sprc_ap_at_k does (fp64, ascending rank), so the numbers are the single-process numbers.
+    gt_idx [nq,G] distinct gallery indices per row, -1 = padding."""
+    from .harness import CIRCO_KS, _circo_dict
+    top_idx = np.asarray(top_idx, dtype=np.int64)
+    gt_idx, tgt_idx = np.asarray(gt_idx, dtype=np.int64), np.asarray(tgt_idx, dtype=np.int64)
+    k = top_idx.shape[1]
+    assert k >= max(CIRCO_KS) or (top_idx[:, -1] < 0).all(), "CIRCO metrics need the merged top-50 (or the whole of a smaller gallery)"
+    assert (tgt_idx >= 0).all() and ((gt_idx >= 0).sum(1) > 0).all(), "every query needs its target and a ground truth in the gallery"
+    ap = np.zeros((len(top_idx), len(CIRCO_KS)), dtype=np.float64)
+    for q in range(len(top_idx)):
+        where = {int(g): p for p, g in enumerate(top_idx[q]) if g >= 0}
+        gts = [int(g) for g in gt_idx[q] if g >= 0]
+        pos = sorted(where[g] for g in gts if g in where)
+        for j, K in enumerate(CIRCO_KS):
+            acc = 0.0
+            for i, r in enumerate(pos):
+                if r < K:
+                    acc += float(i + 1) / float(r + 1)
+            ap[q, j] = acc / float(min(len(gts), K))
+    return _circo_dict(ap, _position(top_idx, tgt_idx))
+
+
 # ---- the three protocols -----------------------------------------------------------------------------------------------
 def _idx(shard: GalleryShard, names: Sequence[str]) -> np.ndarray:
     return np.asarray([shard.name_to_index.get(n, -1) for n in names], dtype=np.int64)
@@ -289,6 +335,36 @@ def generate_cirr_test_dicts_sharded(relative_test_dataset, classic_test_dataset
     grp = np.stack([_idx(shard, g) for g in q.group_members]) if len(q) else np.zeros((0, 6), np.int64)
     _, top_idx, ls = sharded_rank(shard, q, blip_model, listed=grp, group=group, **kw)
     return cirr_test_dicts_from_topk(top_idx.cpu().numpy(), ls.cpu().numpy(), ref, grp, q.pair_ids, shard.names)
+
+
+CIRCO_TOP = 50      # the submission's list length = the largest K of the metric; the protocol removes nothing
+
+
+def _circo_gt_idx(shard: GalleryShard, q: QuerySet):
+    from .harness import circo_indices
+    return circo_indices(shard.names, q.target_names, q.group_members)
+
+
+def compute_circo_val_metrics_sharded(relative_val_dataset, classic_dataset, blip_model, txt_processors, group=None,
+        gallery_batch_size: int = 64, num_workers: int = 2, **kw) -> Dict[str, float]:
+    """Sharded counterpart of harness.compute_circo_val_metrics: the same dict on every rank."""
+    q = circo_val_queries(relative_val_dataset, txt_processors)
+    shard = encode_gallery_shard(classic_dataset, blip_model, reference_names=q.ref_names, group=group,
+                                 batch_size=gallery_batch_size, num_workers=num_workers)
+    gt_idx, tgt_idx = _circo_gt_idx(shard, q)
+    _, top_idx, _ = sharded_rank(shard, q, blip_model, k=CIRCO_TOP, group=group, **kw)
+    return circo_metrics_from_topk(top_idx.cpu().numpy(), gt_idx, tgt_idx)
+
+
+def generate_circo_test_dicts_sharded(relative_test_dataset, classic_dataset, blip_model, txt_processors, group=None,
+        gallery_batch_size: int = 64, num_workers: int = 2, **kw) -> Dict[str, List[str]]:
+    """Sharded counterpart of harness.generate_circo_test_dicts: {query_id: [50 image ids]} on every rank."""
+    from .harness import circo_test_dicts_from_topk
+    q = circo_test_queries(relative_test_dataset, txt_processors)
+    shard = encode_gallery_shard(classic_dataset, blip_model, reference_names=q.ref_names, group=group,
+                                 batch_size=gallery_batch_size, num_workers=num_workers)
+    _, top_idx, _ = sharded_rank(shard, q, blip_model, k=CIRCO_TOP, group=group, **kw)
+    return circo_test_dicts_from_topk(top_idx.cpu().numpy(), q.pair_ids, shard.names)
 
 
 def init_from_env(device_index: Optional[int] = None):

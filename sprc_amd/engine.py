@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -220,6 +220,21 @@ def rank_of(sim: torch.Tensor, listed: torch.Tensor) -> torch.Tensor:
     L.check(lib.sprc_rank_of(sim.data_ptr(), sim.stride(0), listed.data_ptr(), nq, N, listed.shape[1], out.data_ptr(),
                              _stream()), "sprc_rank_of")
     return out
+
+
+def ap_at_k(sim: torch.Tensor, gt: torch.Tensor, ks: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Average precision at every K of `ks` with several ground truths per query (sprc_ap_at_k; the CIRCO metric):
+    gt [nq,G] gallery indices, -1 = padding, no duplicates within a row -> (ap [nq,len(ks)] fp64, rank [nq,G] int32 as `rank_of`)."""
+    lib = L.load()
+    assert sim.dtype == torch.float32 and sim.stride(-1) == 1
+    gt = gt.to(device=sim.device, dtype=torch.int32).contiguous()
+    nq, N = sim.shape
+    kk = (C.c_int32 * len(ks))(*[int(k) for k in ks])
+    ap = torch.empty((nq, len(ks)), dtype=torch.float64, device=sim.device)
+    rank = torch.empty_like(gt)
+    L.check(lib.sprc_ap_at_k(sim.data_ptr(), sim.stride(0), gt.data_ptr(), nq, N, gt.shape[1], kk, len(ks), ap.data_ptr(),
+                             rank.data_ptr(), _stream()), "sprc_ap_at_k")
+    return ap, rank
 
 
 # --------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Evaluation harness of the retrieval path: gallery feature extraction, query prediction loops and
 Recall@K metrics, with the reference's function names, arguments and return values
 (src/utils.py:46-77,141-148; src/validate_blip.py:24-57,149-207,232-285,359-410;
-src/cirr_test_submission.py:61-190) so the reference's scripts can import them unchanged.
+src/cirr_test_submission.py:61-190) so the reference's scripts can import them unchanged.  The CIRCO functions at the
+end have no counterpart there: the reference ships the dataset class (src/data_utils.py:289-426) without an evaluator.
 
 What differs is HOW the metrics are computed: the reference sorts every row of `1 - sim` with
 torch.argsort and then runs O(nq*N) numpy string comparisons (validate_blip.py:253-271).  Here the
@@ -36,9 +37,19 @@ def collate_fn(batch: list):
     return torch.utils.data.dataloader.default_collate(batch)
 
 
+def _pair(item):
+    """A classic CIRCO item {img, img_id} (data_utils.py:412-415) as the (name, image) pair of the other galleries."""
+    return (item["img_id"], item["img"]) if isinstance(item, dict) else item
+
+
+def _collate_gallery(batch: list):
+    """`collate_fn` for a classic (gallery) dataset of any of the three benchmarks."""
+    return collate_fn([_pair(b) for b in batch if b is not None])
+
+
 def _collate_ragged(batch: list):
     """(names, [uint8 HWC tensors of different sizes]) with `None` items dropped."""
-    batch = [b for b in batch if b is not None]
+    batch = [_pair(b) for b in batch if b is not None]
     return [b[0] for b in batch], [b[1] for b in batch]
 
 
@@ -155,6 +166,7 @@ def usable_cores() -> int:
 def extract_index_blip_features(dataset, blip_model, save_memory: bool = False, batch_size: Optional[int] = None, num_workers: int = 2,
                                 keep_raw=True, raw_dtype: Optional[torch.dtype] = None):
     """-> ((feats[N,32,256], raw), names[N])   (src/utils.py:46-77)
+    dataset: a classic CIRRDataset / FashionIQDataset, or a classic CIRCODataset (whose {img, img_id} items are read as pairs).
 
     keep_raw=True (the reference's behaviour): raw = the stacked [N,257,D] fp32 tensor.
     keep_raw=<collection of names> (or False): raw = a `RawStore` holding the embeddings of those images only
@@ -177,7 +189,7 @@ def extract_index_blip_features(dataset, blip_model, save_memory: bool = False, 
         loader = _ThreadLoader(dataset, batch_size, threads=int(os.environ.get("SPRC_DECODE_THREADS") or max(2, min(12, usable_cores() - 2))))
     else:
         loader = DataLoader(dataset=dataset, batch_size=batch_size, num_workers=num_workers, pin_memory=gpu_tf is None and _pin(dataset),
-                            collate_fn=_collate_ragged if gpu_tf is not None else collate_fn, multiprocessing_context=ctx,
+                            collate_fn=_collate_ragged if gpu_tf is not None else _collate_gallery, multiprocessing_context=ctx,
                             persistent_workers=False)
     feats, raws, names = [], [], []
     split = getattr(dataset, "split", "")
@@ -472,3 +484,126 @@ def generate_cirr_test_dicts(relative_test_dataset, blip_model, index_features, 
                 tg = torch.stack([name_to_feat[index_names[int(i)]] for i in cand.reshape(-1)]).to(blip_model.device)
                 return blip_model.inference_rerank(refs, tg, [captions[q] for q in rows]).view(len(rows), -1)
     return cirr_test_dicts_from_sim(sim, ref, grp, pairs_id, index_names, rerank_fn=rerank_fn)
+
+
+# ---- CIRCO: validation metrics (mAP@K over several ground truths) and test submission ---------------------------------
+# No reference counterpart.  The metric is the benchmark's published protocol on this project's ranking contract
+# (include/sprc.h, sprc_ap_at_k): the reference image stays in the order, as on the FashionIQ path (validate_blip.py:49-51).
+CIRCO_KS = (5, 10, 25, 50)
+
+
+def _circo_queries(relative_dataset) -> List[dict]:
+    """Metadata of every query; through `CIRCODataset.query` no image file is opened."""
+    if hasattr(relative_dataset, "query"):
+        return [relative_dataset.query(i) for i in range(len(relative_dataset))]
+    return [item for item in (relative_dataset[i] for i in range(len(relative_dataset))) if item is not None]
+
+
+def circo_reference_ids(relative_dataset) -> List[str]:
+    """Ids of the images some query uses as its reference: what `keep_raw` of a CIRCO gallery pass must name (the raw
+    embeddings of all 123 403 gallery images would be 178 GB)."""
+    return [q["reference_imd_id"] for q in _circo_queries(relative_dataset)]
+
+
+def _circo_fuse_and_score(blip_model, queries: List[dict], index_names, index_features, txt_processors, batch_size, reference_kv):
+    name_to_feat = reference_kv if reference_kv is not None else dict(zip(index_names, index_features[1]))
+    dev = blip_model.device
+    feats = index_features[0].to(dev)
+    sims, captions_all = [], []
+    for s in tqdm(range(0, len(queries), batch_size)):
+        batch = queries[s:s + batch_size]
+        captions = [txt_processors["eval"](q["relative_caption"]) for q in batch]
+        ref_feats = _stack_refs(name_to_feat, [q["reference_imd_id"] for q in batch]).to(dev)
+        sims.append(blip_model.inference(ref_feats, feats, captions))
+        captions_all += captions
+    return torch.vstack(sims), captions_all
+
+
+def generate_circo_val_predictions(blip_model, relative_val_dataset, index_names: List[str], index_features, txt_processors,
+                                   batch_size: int = 32, num_workers: int = 0, reference_kv: Optional[ReferenceKVMap] = None):
+    """-> (sim[nq,N], reference_ids, target_ids, gt_ids (one list per query, unpadded), query_ids, captions)"""
+    del num_workers                     # (queries are metadata: see _query_loader)
+    print("Compute CIRCO validation predictions")
+    queries = _circo_queries(relative_val_dataset)
+    sim, captions = _circo_fuse_and_score(blip_model, queries, index_names, index_features, txt_processors, batch_size, reference_kv)
+    return (sim, [q["reference_imd_id"] for q in queries], [q["target_img_id"] for q in queries],
+            [[g for g in q["gt_img_ids"] if g != ""] for q in queries], [q["query_id"] for q in queries], captions)
+
+
+def circo_indices(index_names: Sequence[str], target_ids: Sequence[str], gt_ids: Sequence[Sequence[str]]):
+    """-> (gt_idx[nq,G] int64 padded with -1, tgt_idx[nq]): gallery indices of the DISTINCT ground truths of every query
+    (in list order) and of its target.  A query without ground truths, or with one that is not in the gallery, is an error."""
+    n2i = {n: i for i, n in enumerate(index_names)}
+    rows = []
+    for q, (tgt, gts) in enumerate(zip(target_ids, gt_ids)):
+        gts = list(dict.fromkeys(g for g in gts if g != ""))
+        if not gts:
+            raise ValueError(f"CIRCO query {q} has no ground truth")
+        missing = [g for g in [tgt, *gts] if g not in n2i]
+        if missing:
+            raise ValueError(f"CIRCO query {q}: image(s) {missing[:3]} are not in the gallery")
+        rows.append([n2i[g] for g in gts])
+    G = max((len(r) for r in rows), default=1)
+    gt_idx = np.full((len(rows), G), -1, dtype=np.int64)
+    for q, r in enumerate(rows):
+        gt_idx[q, :len(r)] = r
+    return gt_idx, np.asarray([n2i[t] for t in target_ids], dtype=np.int64)
+
+
+def circo_metrics_from_sim(sim: torch.Tensor, gt_idx, tgt_idx) -> Dict[str, float]:
+    """-> {circo_map_at{5,10,25,50}, circo_recall_at{5,10,25,50}} in percent, means in float64.  One sprc_ap_at_k call gives
+    AP@K and the rank of every ground truth; Recall@K is [rank(target) < K], the target's rank taken from that call when
+    the target is one of the ground truths (it always is in the published annotations), from sprc_rank_of otherwise."""
+    gt_idx, tgt_idx = np.asarray(gt_idx, dtype=np.int64), np.asarray(tgt_idx, dtype=np.int64)
+    if gt_idx.shape[1] > 32:
+        raise ValueError(f"{gt_idx.shape[1]} ground truths in one query: sprc_ap_at_k takes up to 32")
+    sim = sim.contiguous()
+    ap, rank = E.ap_at_k(sim, torch.from_numpy(gt_idx), CIRCO_KS)
+    ap, rank = ap.cpu().numpy(), rank.cpu().numpy().astype(np.int64)
+    hit = (gt_idx == tgt_idx[:, None]) & (gt_idx >= 0)
+    r_t = np.where(hit.any(1), rank[np.arange(len(rank)), hit.argmax(1)], -1)
+    rest = np.nonzero(~hit.any(1))[0]
+    if len(rest):
+        r_t[rest] = E.rank_of(sim[torch.from_numpy(rest).to(sim.device)], torch.from_numpy(tgt_idx[rest, None])).cpu().numpy()[:, 0]
+    if (r_t < 0).any():
+        raise ValueError("every CIRCO query needs its target in the gallery")
+    return _circo_dict(ap, r_t)
+
+
+def _circo_dict(ap: np.ndarray, r_t: np.ndarray) -> Dict[str, float]:
+    """ap[nq, len(CIRCO_KS)] fp64, r_t[nq] target ranks -> the eight CIRCO numbers in percent (float64 means)."""
+    out = {f"circo_map_at{k}": 100.0 * float(ap[:, i].mean(dtype=np.float64)) for i, k in enumerate(CIRCO_KS)}
+    out.update({f"circo_recall_at{k}": 100.0 * float((r_t < k).mean(dtype=np.float64)) for k in CIRCO_KS})
+    return out
+
+
+def compute_circo_val_metrics(relative_val_dataset, blip_model, index_features, index_names: List[str], txt_processors,
+                              reuse_reference_kv: bool = False) -> Dict[str, float]:
+    """-> {circo_map_at{5,10,25,50}, circo_recall_at{5,10,25,50}}; reuse_reference_kv as in compute_cirr_val_metrics."""
+    rkv = None
+    if reuse_reference_kv:
+        rkv = build_reference_kv(blip_model, index_names, index_features, circo_reference_ids(relative_val_dataset))
+    sim, _, target_ids, gt_ids, _, _ = generate_circo_val_predictions(
+        blip_model, relative_val_dataset, index_names, index_features, txt_processors, reference_kv=rkv)
+    print("Compute CIRCO validation metrics")
+    gt_idx, tgt_idx = circo_indices(index_names, target_ids, gt_ids)
+    return circo_metrics_from_sim(sim, gt_idx, tgt_idx)
+
+
+def circo_test_dicts_from_topk(top_idx, query_ids: Sequence[str], index_names: Sequence[str]) -> Dict[str, List[str]]:
+    """query id -> the ids of its first 50 gallery images (fewer when the gallery is smaller), from top-k indices."""
+    names = np.asarray(index_names)
+    top_idx = np.asarray(top_idx, dtype=np.int64)
+    return {str(qid): names[[i for i in row[:50] if i >= 0]].tolist() for qid, row in zip(query_ids, top_idx)}
+
+
+def generate_circo_test_dicts(relative_test_dataset, blip_model, index_features, index_names: List[str], txt_processors,
+                              batch_size: int = 32) -> Dict[str, List[str]]:
+    """-> {query_id: [50 image ids]}: the dataset's `img_id` strings in ranking order (sprc_topk), the reference image
+    not removed.  The layout follows the benchmark's public description of a submission (one JSON object, query id ->
+    ranked image ids); the evaluation server's exact format cannot be checked offline."""
+    print("Compute CIRCO test predictions")
+    queries = _circo_queries(relative_test_dataset)
+    sim, _ = _circo_fuse_and_score(blip_model, queries, index_names, index_features, txt_processors, batch_size, None)
+    _, idx = E.topk(sim.contiguous(), 50)
+    return circo_test_dicts_from_topk(idx.cpu().numpy(), [q["query_id"] for q in queries], index_names)

@@ -10,7 +10,10 @@ The reference re-encodes the whole gallery on every run (`src/utils.py:46-77` re
                                     fp16 / bf16: the format the engine rounds them to anyway when it reads them (the K|V
                                     projection operand of the fusion pass and of the rerank): half the bytes, the same bits
                                     downstream (the rounding is idempotent); load_index hands them back as fp32
-    metadata   names (JSON list, row order), backbone, dtype the features were computed in, format version,
+                                    With `raw_names` (a gallery too large to keep every image's embeddings: CIRCO's 123 403
+                                    images would be 178 GB) raw holds the rows of those images only, in that order, and
+                                    load_index hands back a `harness.RawStore`
+    metadata   names (JSON list, row order), raw_names (optional JSON list), backbone, dtype the features were computed in, format version,
                checkpoint_sha256 = fingerprint of the state dict that produced the features (blip_validate refuses a store
                written by another checkpoint)
 
@@ -29,12 +32,16 @@ FORMAT = "sprc-index-1"
 
 
 def save_index(path, feats: torch.Tensor, names: Sequence[str], raw: Optional[torch.Tensor] = None, backbone: str = "",
-               compute_dtype: str = "", checkpoint_sha256: str = "", raw_dtype: torch.dtype = torch.float32) -> None:
+               compute_dtype: str = "", checkpoint_sha256: str = "", raw_dtype: torch.dtype = torch.float32,
+               raw_names: Optional[Sequence[str]] = None) -> None:
+    """raw_names: `raw` holds the embeddings of these gallery images only (one row each, in this order)."""
     from safetensors.torch import save_file
     if feats.dim() != 3 or feats.shape[1] != 32:
         raise ValueError(f"feats must be [N,32,E], got {tuple(feats.shape)}")
-    if len(names) != feats.shape[0] or (raw is not None and raw.shape[0] != feats.shape[0]):
+    if len(names) != feats.shape[0] or (raw is not None and raw.shape[0] != (feats.shape[0] if raw_names is None else len(raw_names))):
         raise ValueError("names / raw must have one entry per gallery row")
+    if raw_names is not None and (raw is None or not set(raw_names) <= set(names)):
+        raise ValueError("raw_names must name gallery rows whose embeddings are given in `raw`")
     if len(set(names)) != len(names):
         raise ValueError("gallery names must be unique (they are the join key of the relative datasets)")
     tensors = {"feats": feats.detach().to("cpu", torch.float32).contiguous()}
@@ -44,6 +51,8 @@ def save_index(path, feats: torch.Tensor, names: Sequence[str], raw: Optional[to
         tensors["raw"] = raw.detach().to(raw_dtype).to("cpu").contiguous()          # rounded where the tensor lives (the GPU), then copied
     meta = {"format": FORMAT, "names": json.dumps(list(names)), "backbone": backbone, "compute_dtype": compute_dtype,
             "checkpoint_sha256": checkpoint_sha256}
+    if raw_names is not None:
+        meta["raw_names"] = json.dumps(list(raw_names))
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     save_file(tensors, str(path), metadata=meta)
@@ -64,4 +73,8 @@ def load_index(path, device="cpu", with_raw: bool = True) -> Tuple[Tuple[torch.T
         raise ValueError(f"{path}: {len(names)} names for {feats.shape[0]} rows")
     feats = feats.to(device)
     raw = raw.to(device).float() if raw is not None else None
-    return (feats, raw), names, {k: v for k, v in meta.items() if k != "names"}
+    if raw is not None and "raw_names" in meta:
+        from .harness import RawStore
+        row_of = {n: i for i, n in enumerate(names)}
+        raw = RawStore(len(names), {row_of[n]: raw[j] for j, n in enumerate(json.loads(meta["raw_names"]))})
+    return (feats, raw), names, {k: v for k, v in meta.items() if k not in ("names", "raw_names")}
