@@ -25,40 +25,30 @@ static const sprc_rowmap ID_MAP = {0, 0, 0};
 
 struct Fp8Scales { const float* w_scale; float a_scale, out_scale; };
 
-static int gemm(hipStream_t st, int dt, int out_dt, int M, int N, int K, const void* A, int64_t lda, const sprc_linear& w,
-                void* C, int64_t ldc, int act = SPRC_ACT_NONE, const float* resid = nullptr, int64_t ldr = 0,
-                sprc_rowmap amap = ID_MAP, sprc_rowmap cmap = ID_MAP, void* scratch = nullptr, size_t scratch_bytes = 0,
-                const Fp8Scales* q = nullptr, int64_t ldw = 0, int k8 = 0, int k_alg = 0) {
-    // k_alg: the ALGORITHMIC reduction length for the profiler when it differs from K (the patch embedding launches its zero-padded K)
+// One sprc_gemm launch: C[M, N] (out_dt) = A[M, K] (dt) . w^T + bias.  What every product has is given at construction, the rest
+// by name; whatever is not named stays zero (no activation, no residual, identity row maps, ldw = K, a plain product).
+struct Gemm {
     sprc_gemm_args g;
-    memset(&g, 0, sizeof(g));
-    g.k8 = k8; g.k_alg = k_alg;
-    if (q != nullptr) { g.w_scale = q->w_scale; g.a_scale = q->a_scale; g.out_scale = q->out_scale; }
-    g.M = M; g.N = N; g.K = K; g.dtype = dt; g.out_dtype = out_dt; g.act = act;
-    g.A = A; g.lda = lda; g.amap = amap;
-    g.W = w.w; g.ldw = ldw > 0 ? ldw : K; g.bias = w.b;
-    g.resid = resid; g.ldr = ldr;
-    g.C = C; g.ldc = ldc; g.cmap = cmap;
-    g.scratch = scratch; g.scratch_bytes = scratch_bytes;
-    return sprc_gemm(&g, st);
-}
-
-// two products of identical shape in one launch (sprc_gemm_pair): w0 on the rows amap0 -> cmap0, w1 on amap1 -> cmap1
-static int gemm2(hipStream_t st, int dt, int out_dt, int M, int N, int K, const void* A, int64_t lda, const sprc_linear& w0,
-                 const sprc_linear& w1, void* C, int64_t ldc, int act, const float* resid, int64_t ldr, sprc_rowmap amap0,
-                 sprc_rowmap amap1, sprc_rowmap cmap0, sprc_rowmap cmap1, int64_t ldw = 0, int k8 = 0) {
-    sprc_gemm_args g[2];
-    memset(g, 0, sizeof(g));
-    for (int i = 0; i < 2; ++i) {
-        g[i].k8 = k8;
-        g[i].M = M; g[i].N = N; g[i].K = K; g[i].dtype = dt; g[i].out_dtype = out_dt; g[i].act = act;
-        g[i].A = A; g[i].lda = lda; g[i].amap = i ? amap1 : amap0;
-        g[i].W = (i ? w1 : w0).w; g[i].ldw = ldw > 0 ? ldw : K; g[i].bias = (i ? w1 : w0).b;
-        g[i].resid = resid; g[i].ldr = ldr;
-        g[i].C = C; g[i].ldc = ldc; g[i].cmap = i ? cmap1 : cmap0;
+    Gemm(int dt, int out_dt, int M, int N, int K, const void* A, int64_t lda, const sprc_linear& w, void* C, int64_t ldc) {
+        memset(&g, 0, sizeof(g));
+        g.M = M; g.N = N; g.K = K; g.dtype = dt; g.out_dtype = out_dt;
+        g.A = A; g.lda = lda;
+        g.W = w.w; g.ldw = K; g.bias = w.b;
+        g.C = C; g.ldc = ldc;
     }
-    return sprc_gemm_pair(&g[0], &g[1], st);
-}
+    Gemm& act(int a) { g.act = a; return *this; }
+    Gemm& resid(const float* r, int64_t ldr) { g.resid = r; g.ldr = ldr; return *this; }
+    Gemm& rows(sprc_rowmap amap, sprc_rowmap cmap) { g.amap = amap; g.cmap = cmap; return *this; }
+    Gemm& scratch(void* p, size_t bytes) { g.scratch = p; g.scratch_bytes = bytes; return *this; }
+    Gemm& fp8(const Fp8Scales& q) { g.w_scale = q.w_scale; g.a_scale = q.a_scale; g.out_scale = q.out_scale; return *this; }
+    // split-precision operands: weight rows of pitch ldw (fp16 units), k8 e4m3 correction elements behind the K fp16 ones (0: hi segment only)
+    Gemm& split(int64_t ldw, int k8) { g.ldw = ldw; g.k8 = k8; return *this; }
+    // the ALGORITHMIC reduction length for the profiler when it differs from K (the patch embedding launches its zero-padded K)
+    Gemm& k_alg(int k) { g.k_alg = k; return *this; }
+    int run(hipStream_t st) const { return sprc_gemm(&g, st); }
+};
+// two products of identical shape in one launch (sprc_gemm_pair): they differ in the weights and in the row maps' offsets
+static int run_pair(const Gemm& a, const Gemm& b, hipStream_t st) { return sprc_gemm_pair(&a.g, &b.g, st); }
 
 // y = LN(x [+ add16]); sum32 (optional) receives x + add16 (the residual-stream update of a pre-LN block)
 static int lnorm(hipStream_t st, int dt, int M, int D, const float* x, const float* gam, const float* bet, float eps,
@@ -83,25 +73,34 @@ struct KvSrc {
     int64_t ld;                                      // elements per token row: n_cross * 2 * hidden
 };
 
-static int attn(hipStream_t st, int dt, int B, int H, int Tq, int Tk, int dh, const void* q, int64_t ldq, const void* k,
-                int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo, const float* mask, float scale,
-                const KvSrc* two = nullptr, size_t seg2_off = 0, bool out_x3 = false) {
+// One sprc_attention launch, described like Gemm: the operands at construction, key mask / gathered keys / split output by name.
+struct Attn {
     sprc_attention_args a;
-    memset(&a, 0, sizeof(a));
-    a.out_x3 = out_x3 ? 1 : 0;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.head_dim = dh; a.dtype = dt;
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out = out; a.ldo = ldo;
-    a.key_mask = mask; a.scale = scale;
-    if (two != nullptr) {                            // k / v already point at segment 1; segment 2 at the same byte offsets
-        a.kv_index = two->ia;
-        if (two->b != nullptr) {
-            a.k2 = (const char*)two->b + seg2_off; a.ldk2 = two->ld;
-            a.v2 = (const char*)a.k2 + (size_t)((const char*)v - (const char*)k); a.ldv2 = two->ld;
-            a.Tk2 = two->Tb; a.kv2_index = two->ib;
-        }
+    Attn(int dt, int B, int H, int Tq, int Tk, int dh, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+         int64_t ldv, void* out, int64_t ldo, float scale) {
+        memset(&a, 0, sizeof(a));
+        a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.head_dim = dh; a.dtype = dt;
+        a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out = out; a.ldo = ldo;
+        a.scale = scale;
     }
-    return sprc_attention(&a, st);
-}
+    // self-attention over one fused q|k|v buffer [B T, 3 D]
+    Attn(int dt, int B, int H, int T, int dh, const void* qkv, int D, void* out, int64_t ldo, float scale)
+        : Attn(dt, B, H, T, T, dh, qkv, 3 * D, (const char*)qkv + D * dtype_size(dt), 3 * D, (const char*)qkv + 2 * D * dtype_size(dt), 3 * D, out,
+               ldo, scale) {}
+    Attn& mask(const float* key_mask) { a.key_mask = key_mask; return *this; }
+    Attn& out_x3(bool on) { a.out_x3 = on ? 1 : 0; return *this; }
+    // keys of `src` through its index arrays: k / v already point at segment 1; segment 2 at the same byte offset `off` of its rows
+    Attn& gather(const KvSrc& src, size_t off) {
+        a.kv_index = src.ia;
+        if (src.b != nullptr) {
+            a.k2 = (const char*)src.b + off; a.ldk2 = src.ld;
+            a.v2 = (const char*)a.k2 + (size_t)((const char*)a.v - (const char*)a.k); a.ldv2 = src.ld;
+            a.Tk2 = src.Tb; a.kv2_index = src.ib;
+        }
+        return *this;
+    }
+    int run(hipStream_t st) const { return sprc_attention(&a, st); }
+};
 
 // The residual adds stay in the branch GEMMs' fp32 + residual epilogues.  Folding them into the LayerNorm kernels (branch GEMMs
 // writing fp16 deltas, sprc_layernorm_args.add16) was measured on MI355X and removed: GEMM class 83.9 -> 78.5 ms per step (872 -> 932
@@ -194,86 +193,66 @@ static int qf_stack(const sprc_qformer_model* m, hipStream_t st, QfBufs& q, int 
     const size_t es = dtype_size(dt);
     const sprc_rowmap qmap = {Lq, S, 0}, tmap = {S - Lq, S, Lq};
     const bool split = with_enc && S > Lq;         // rows [:Lq] and [Lq:] take different paths
-    // y = act(in . W^T + b) of layer kind `kind` over `width` input columns, into a compute-dtype (or x3) buffer
+    struct Rows { int n; sprc_rowmap map; };       // a row set of the batch: n rows in all, at `map` of every sample's S
+    const Rows all{R, ID_MAP}, need{B * need_n, {need_n, S, need_lo}}, qrows{B * Lq, split ? qmap : ID_MAP}, trows{B * (S - Lq), tmap};
+    // y = in . W^T + b of layer kind `kind` over `width` input columns, into a compute-dtype (or x3) buffer
     auto lin = [&](int kind, int rows, int N, int width, const void* in, int64_t lda, const sprc_linear& w, int odt, void* out,
-                   int64_t ldc, int act, sprc_rowmap amap, sprc_rowmap cmap) -> int {
-        return gemm(st, dt, odt, rows, N, width, in, lda, w, out, ldc, act, nullptr, 0, amap, cmap, nullptr, 0, nullptr,
-                    wld(kind, width), k8of(kind, width));
-    };
+                   int64_t ldc) { return Gemm(dt, odt, rows, N, width, in, lda, w, out, ldc).split(wld(kind, width), k8of(kind, width)); };
     // a = LN(dense(in) + res): branch GEMM of layer kind `kind` over `width` input columns, post-LN into (o32, o16)
     auto branch = [&](int kind, int rows, int width, int64_t lda, const void* in, const sprc_linear& w, const float* res,
                       const float* lw, const float* lb, float* o32, void* o16, sprc_rowmap amap, sprc_rowmap cmap) -> int {
-        RUN(gemm(st, dt, SPRC_F32, rows, Hd, width, in, lda, w, q.t32, Hd, SPRC_ACT_NONE, res, Hd, amap, cmap, nullptr, 0,
-                 nullptr, wld(kind, width), k8of(kind, width)));
+        RUN(lin(kind, rows, Hd, width, in, lda, w, SPRC_F32, q.t32, Hd).resid(res, Hd).rows(amap, cmap).run(st));
         return lnorm(st, adt, rows, Hd, q.t32, lw, lb, m->ln_eps, o32, o16, cmap);
+    };
+    // the FFN of the rows `r` through one set of weights: q.a16 -> GELU hidden in q.ffn (rows packed) -> post-LN into (x32, x16)
+    auto ffn = [&](const Rows& r, const sprc_linear& in, const sprc_linear& out, const float* lw, const float* lb) -> int {
+        RUN(lin(SPRC_X3_FFN_IN, r.n, F, Hd, q.a16, KH, in, fdt, q.ffn, KF).act(SPRC_ACT_GELU).rows(r.map, ID_MAP).run(st));
+        return branch(SPRC_X3_FFN_OUT, r.n, F, KF, q.ffn, out, q.a32, lw, lb, x32, x16, ID_MAP, r.map);
     };
     const bool prune = need_n > 0 && need_n < S && (need_n & (need_n - 1)) == 0 &&
                        (with_enc ? (split && need_lo == 0 && need_n == Lq) : true);
     for (int l = 0; l < m->n_layers; ++l) {
         const sprc_qf_layer& L = m->layers[l];
+        // the row sets of this layer: the output branch of the self-attention (and, without an encoder, the text FFN) on `sa`; with an
+        // encoder the query path on `rq` and the text path on `trows`.  Pruning the last layer changes nothing but these: sa = the
+        // needed rows; with an encoder they are the query rows and there is no text path.
+        const bool pruned = prune && l == m->n_layers - 1;
+        const Rows& sa = pruned ? need : all;
         // self-attention over all S rows
-        RUN(lin(SPRC_X3_QKV, R, 3 * Hd, Hd, x16, KH, L.qkv, dt, q.qkv, 3 * Hd, SPRC_ACT_NONE, ID_MAP, ID_MAP));
-        RUN(attn(st, dt, B, H, S, S, dh, q.qkv, 3 * Hd, (char*)q.qkv + Hd * es, 3 * Hd, (char*)q.qkv + 2 * Hd * es, 3 * Hd,
-                 q.ctx, KC, mask, sc, nullptr, 0, lay.ctx));
-        if (prune && l == m->n_layers - 1) {
-            // last layer, rows nobody reads dropped: nmap = the needed rows of every sample
-            const sprc_rowmap nmap = {need_n, S, need_lo};
-            const int Rn = B * need_n;
-            RUN(branch(SPRC_X3_ATTN_OUT, Rn, Hd, KC, q.ctx, L.attn_out, x32, L.attn_ln_w, L.attn_ln_b, q.a32, q.a16, nmap, nmap));
-            if (with_enc) {                       // the needed rows are the query rows: cross-attention + query FFN as in any layer, no text FFN
-                if (L.has_cross) {
-                    RUN(lin(SPRC_X3_CROSS_Q, Rn, Hd, Hd, q.a16, KH, L.cq, dt, q.cq, Hd, SPRC_ACT_NONE, nmap, ID_MAP));
-                    const size_t off = (size_t)L.cross_index * 2 * Hd * es;
-                    const char* kp = (const char*)kvs->a + off;
-                    const bool plain = kvs->b == nullptr && kvs->ia == nullptr;
-                    RUN(attn(st, dt, B, H, Lq, kvs->Ta, dh, q.cq, Hd, kp, kvs->ld, kp + Hd * es, kvs->ld, q.ctx, KC, nullptr, sc,
-                             plain ? nullptr : kvs, off, lay.ctx));
-                    RUN(branch(SPRC_X3_CROSS_OUT, Rn, Hd, KC, q.ctx, L.cross_out, q.a32, L.cross_ln_w, L.cross_ln_b, q.a32, q.a16, ID_MAP, nmap));
-                }
-                RUN(lin(SPRC_X3_FFN_IN, Rn, F, Hd, q.a16, KH, L.ffn_q_in, fdt, q.ffn, KF, SPRC_ACT_GELU, nmap, ID_MAP));
-                RUN(branch(SPRC_X3_FFN_OUT, Rn, F, KF, q.ffn, L.ffn_q_out, q.a32, L.ffn_q_ln_w, L.ffn_q_ln_b, x32, x16, ID_MAP, nmap));
-            } else {
-                RUN(lin(SPRC_X3_FFN_IN, Rn, F, Hd, q.a16, KH, L.ffn_t_in, fdt, q.ffn, KF, SPRC_ACT_GELU, nmap, ID_MAP));
-                RUN(branch(SPRC_X3_FFN_OUT, Rn, F, KF, q.ffn, L.ffn_t_out, q.a32, L.ffn_t_ln_w, L.ffn_t_ln_b, x32, x16, ID_MAP, nmap));
-            }
-            break;
+        RUN(lin(SPRC_X3_QKV, R, 3 * Hd, Hd, x16, KH, L.qkv, dt, q.qkv, 3 * Hd).run(st));
+        RUN(Attn(dt, B, H, S, dh, q.qkv, Hd, q.ctx, KC, sc).mask(mask).out_x3(lay.ctx).run(st));
+        RUN(branch(SPRC_X3_ATTN_OUT, sa.n, Hd, KC, q.ctx, L.attn_out, x32, L.attn_ln_w, L.attn_ln_b, q.a32, q.a16, sa.map, sa.map));
+        if (!with_enc) {
+            RUN(ffn(sa, L.ffn_t_in, L.ffn_t_out, L.ffn_t_ln_w, L.ffn_t_ln_b));
+            continue;
         }
-        RUN(branch(SPRC_X3_ATTN_OUT, R, Hd, KC, q.ctx, L.attn_out, x32, L.attn_ln_w, L.attn_ln_b, q.a32, q.a16, ID_MAP, ID_MAP));
-        if (with_enc) {
-            const sprc_rowmap rq = split ? qmap : ID_MAP;
-            const int Rq = B * Lq;
-            if (L.has_cross) {
-                RUN(lin(SPRC_X3_CROSS_Q, Rq, Hd, Hd, q.a16, KH, L.cq, dt, q.cq, Hd, SPRC_ACT_NONE, rq, ID_MAP));
-                const size_t off = (size_t)L.cross_index * 2 * Hd * es;          // this layer's K|V block inside a token row
-                const char* kp = (const char*)kvs->a + off;
-                const bool plain = kvs->b == nullptr && kvs->ia == nullptr;
-                RUN(attn(st, dt, B, H, Lq, kvs->Ta, dh, q.cq, Hd, kp, kvs->ld, kp + Hd * es, kvs->ld, q.ctx, KC, nullptr, sc,
-                         plain ? nullptr : kvs, off, lay.ctx));
-                RUN(branch(SPRC_X3_CROSS_OUT, Rq, Hd, KC, q.ctx, L.cross_out, q.a32, L.cross_ln_w, L.cross_ln_b, q.a32, q.a16, ID_MAP, rq));
-            }
-            if (split && S - Lq == Lq) {
-                // query rows and text rows of every sample go through different FFN weights (Qformer.py:455-475): the two
-                // products have the same shape, so each pair is ONE launch (sprc_gemm_pair) -- 360 + 360 tiles instead of two
-                // 1.4-round grids for the up projection, 90 + 90 instead of two third-empty grids for the down projection.
-                // The hidden activations keep the rows' natural positions in q.ffn [R, F].
-                RUN(gemm2(st, dt, fdt, Rq, F, Hd, q.a16, KH, L.ffn_q_in, L.ffn_t_in, q.ffn, KF, SPRC_ACT_GELU, nullptr, 0,
-                          qmap, tmap, qmap, tmap, wld(SPRC_X3_FFN_IN, Hd), k8of(SPRC_X3_FFN_IN, Hd)));
-                RUN(gemm2(st, dt, SPRC_F32, Rq, Hd, F, q.ffn, KF, L.ffn_q_out, L.ffn_t_out, q.t32, Hd, SPRC_ACT_NONE,
-                          q.a32, Hd, qmap, tmap, qmap, tmap, wld(SPRC_X3_FFN_OUT, F), k8of(SPRC_X3_FFN_OUT, F)));
-                RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_q_ln_w, L.ffn_q_ln_b, m->ln_eps, x32, x16, qmap));
-                RUN(lnorm(st, adt, Rq, Hd, q.t32, L.ffn_t_ln_w, L.ffn_t_ln_b, m->ln_eps, x32, x16, tmap));
-            } else {
-                RUN(lin(SPRC_X3_FFN_IN, Rq, F, Hd, q.a16, KH, L.ffn_q_in, fdt, q.ffn, KF, SPRC_ACT_GELU, rq, ID_MAP));
-                RUN(branch(SPRC_X3_FFN_OUT, Rq, F, KF, q.ffn, L.ffn_q_out, q.a32, L.ffn_q_ln_w, L.ffn_q_ln_b, x32, x16, ID_MAP, rq));
-                if (split) {
-                    const int Rt = B * (S - Lq);
-                    RUN(lin(SPRC_X3_FFN_IN, Rt, F, Hd, q.a16, KH, L.ffn_t_in, fdt, q.ffn, KF, SPRC_ACT_GELU, tmap, ID_MAP));
-                    RUN(branch(SPRC_X3_FFN_OUT, Rt, F, KF, q.ffn, L.ffn_t_out, q.a32, L.ffn_t_ln_w, L.ffn_t_ln_b, x32, x16, ID_MAP, tmap));
-                }
-            }
+        const Rows& rq = pruned ? need : qrows;
+        const bool text = split && !pruned;
+        if (L.has_cross) {
+            RUN(lin(SPRC_X3_CROSS_Q, rq.n, Hd, Hd, q.a16, KH, L.cq, dt, q.cq, Hd).rows(rq.map, ID_MAP).run(st));
+            const size_t off = (size_t)L.cross_index * 2 * Hd * es;          // this layer's K|V block inside a token row
+            const char* kp = (const char*)kvs->a + off;
+            RUN(Attn(dt, B, H, Lq, kvs->Ta, dh, q.cq, Hd, kp, kvs->ld, kp + Hd * es, kvs->ld, q.ctx, KC, sc).gather(*kvs, off).out_x3(lay.ctx).run(st));
+            RUN(branch(SPRC_X3_CROSS_OUT, rq.n, Hd, KC, q.ctx, L.cross_out, q.a32, L.cross_ln_w, L.cross_ln_b, q.a32, q.a16, ID_MAP, rq.map));
+        }
+        if (text && S - Lq == Lq) {
+            // query rows and text rows of every sample go through different FFN weights (Qformer.py:455-475): the two
+            // products have the same shape, so each pair is ONE launch (sprc_gemm_pair) -- 360 + 360 tiles instead of two
+            // 1.4-round grids for the up projection, 90 + 90 instead of two third-empty grids for the down projection.
+            // The hidden activations keep the rows' natural positions in q.ffn [R, F].
+            auto up = [&](const sprc_linear& w, sprc_rowmap rows) {
+                return lin(SPRC_X3_FFN_IN, rq.n, F, Hd, q.a16, KH, w, fdt, q.ffn, KF).act(SPRC_ACT_GELU).rows(rows, rows);
+            };
+            auto down = [&](const sprc_linear& w, sprc_rowmap rows) {
+                return lin(SPRC_X3_FFN_OUT, rq.n, Hd, F, q.ffn, KF, w, SPRC_F32, q.t32, Hd).resid(q.a32, Hd).rows(rows, rows);
+            };
+            RUN(run_pair(up(L.ffn_q_in, qmap), up(L.ffn_t_in, tmap), st));
+            RUN(run_pair(down(L.ffn_q_out, qmap), down(L.ffn_t_out, tmap), st));
+            RUN(lnorm(st, adt, rq.n, Hd, q.t32, L.ffn_q_ln_w, L.ffn_q_ln_b, m->ln_eps, x32, x16, qmap));
+            RUN(lnorm(st, adt, rq.n, Hd, q.t32, L.ffn_t_ln_w, L.ffn_t_ln_b, m->ln_eps, x32, x16, tmap));
         } else {
-            RUN(lin(SPRC_X3_FFN_IN, R, F, Hd, q.a16, KH, L.ffn_t_in, fdt, q.ffn, KF, SPRC_ACT_GELU, ID_MAP, ID_MAP));
-            RUN(branch(SPRC_X3_FFN_OUT, R, F, KF, q.ffn, L.ffn_t_out, q.a32, L.ffn_t_ln_w, L.ffn_t_ln_b, x32, x16, ID_MAP, ID_MAP));
+            RUN(ffn(rq, L.ffn_q_in, L.ffn_q_out, L.ffn_q_ln_w, L.ffn_q_ln_b));
+            if (text) RUN(ffn(trows, L.ffn_t_in, L.ffn_t_out, L.ffn_t_ln_w, L.ffn_t_ln_b));
         }
     }
     return SPRC_OK;
@@ -293,19 +272,13 @@ static int qf_encode_kv(const sprc_qformer_model* m, hipStream_t st, void* enc16
         enc = enc16;
     }
     const int Nkv = m->n_cross * 2 * m->hidden, Kw = m->enc_width;
-    return gemm(st, m->dtype, m->dtype, E, Nkv, Kw, enc, Kw * (kv3 ? 2 : 1), m->ckv_all, kv_out, Nkv, SPRC_ACT_NONE, nullptr, 0, ID_MAP, ID_MAP, nullptr, 0,
-                nullptr, (int64_t)Kw * ((m->x3 & SPRC_X3_CKV) ? 2 : 1), kv3 ? 2 * Kw : 0);
+    return Gemm(m->dtype, m->dtype, E, Nkv, Kw, enc, Kw * (kv3 ? 2 : 1), m->ckv_all, kv_out, Nkv)
+        .split((int64_t)Kw * ((m->x3 & SPRC_X3_CKV) ? 2 : 1), kv3 ? 2 * Kw : 0).run(st);
 }
 
-// out[rows, embed_dim] (fp32) = proj(hidden rows `amap` of x16): the ITC heads (align_prompt.py:348,385)
-static int head(const sprc_qformer_model* m, hipStream_t st, int cm, int rows, const void* x16, const sprc_linear& w, float* out,
-                sprc_rowmap amap) {
-    const int Hd = m->hidden;
-    return gemm(st, m->dtype, SPRC_F32, rows, m->embed_dim, Hd, x16, x3_layouts(cm).ln ? 2 * Hd : Hd, w, out, m->embed_dim,
-                SPRC_ACT_NONE, nullptr, 0, amap, ID_MAP, nullptr, 0, nullptr, (int64_t)((m->x3 & SPRC_X3_HEADS) ? 2 * Hd : Hd), (cm & SPRC_X3_HEADS) ? 2 * Hd : 0);
-}
-
-static int check_qf(const sprc_qformer_model* m) {
+// ---- what the Q-Former entry points share: `fn` is the entry point's name in its error messages ------------------------------------
+// the model's checks, then the entry point's own arguments
+static int check_qf(const char* fn, const sprc_qformer_model* m, bool args_ok) {
     SPRC_REQUIRE(m && m->layers, "qformer: null model");
     SPRC_REQUIRE(is16(m->dtype) || m->dtype == SPRC_F32, "qformer: bad dtype");
     SPRC_REQUIRE(!m->x3 || m->dtype == SPRC_F16, "qformer: the split-precision mode (x3) needs dtype SPRC_F16");
@@ -313,7 +286,43 @@ static int check_qf(const sprc_qformer_model* m) {
     SPRC_REQUIRE(m->hidden == m->heads * m->head_dim, "qformer: hidden != heads*head_dim");
     SPRC_REQUIRE((m->num_query & (m->num_query - 1)) == 0 && (m->max_txt & (m->max_txt - 1)) == 0,
                  "qformer: num_query and max_txt must be powers of two");
+    SPRC_REQUIRE(args_ok, "%s: bad arguments", fn);
     return SPRC_OK;
+}
+
+// the workspace carved into the buffers of a batch of B; enc_tokens / with_kv: the image tokens the call projects to K|V itself
+static int qf_carve(const char* fn, const sprc_qformer_model* m, int B, int enc_tokens, bool with_kv, void* ws, size_t ws_bytes, QfBufs& q) {
+    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", fn);
+    Bump b(ws, ws_bytes);
+    qf_plan(m, B, enc_tokens, b, q, with_kv);
+    if (!b.ok) {
+        set_error("%s: workspace too small (%zu bytes given)", fn, ws_bytes);
+        return SPRC_EWORKSPACE;
+    }
+    return SPRC_OK;
+}
+
+// the embedded input rows of one pass into (y32, y16): Lq rows of `query` (q_bstride elements between samples, 0 = broadcast), then
+// Lt text rows of `ids` (null: no text); no_img: the text-only row order of sprc_qformer_embed_args
+static int qf_embed(const sprc_qformer_model* m, hipStream_t st, int cm, int B, int Lq, int Lt, const float* query, int64_t q_bstride,
+                    const int64_t* ids, bool no_img, float* y32, void* y16) {
+    sprc_qformer_embed_args e;
+    memset(&e, 0, sizeof(e));
+    e.B = B; e.Lq = Lq; e.Lt = Lt; e.hidden = m->hidden; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : m->dtype;
+    e.query_embeds = query; e.q_bstride = q_bstride;
+    if (ids != nullptr) { e.vocab = m->vocab; e.input_ids = ids; e.word_emb = m->word_emb; e.pos_emb = m->pos_emb; }
+    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
+    e.y32 = y32; e.y16 = y16; e.no_img = no_img ? 1 : 0;
+    return sprc_qformer_embed(&e, st);
+}
+
+// (out32, out16) [rows, embed_dim] = normalize(proj(hidden rows `amap` of x16)): the ITC heads (align_prompt.py:348-350,385)
+static int qf_project(const sprc_qformer_model* m, hipStream_t st, int cm, QfBufs& q, int rows, const void* x16, sprc_rowmap amap,
+                      const sprc_linear& w, float* out32, void* out16) {
+    const int Hd = m->hidden, E = m->embed_dim;
+    RUN(Gemm(m->dtype, SPRC_F32, rows, E, Hd, x16, x3_layouts(cm).ln ? 2 * Hd : Hd, w, q.proj, E).rows(amap, ID_MAP)
+            .split((m->x3 & SPRC_X3_HEADS) ? 2 * Hd : Hd, (cm & SPRC_X3_HEADS) ? 2 * Hd : 0).run(st));
+    return sprc_l2norm_rows(q.proj, E, out32, out16, E, rows, E, m->dtype, st);
 }
 
 }  // namespace sprc
@@ -355,15 +364,10 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
     const float scale = 1.0f / sqrtf((float)m->head_dim);                       // eva_vit.py:74
     SPRC_REQUIRE(!m->patch_x3 || dt == SPRC_F16, "sprc_vit_forward: patch_x3 is a mode of the fp16 model");
     const int patch_k = 3 * m->patch_size * m->patch_size;     // the convolution's own reduction length (588; launched zero padded)
-    if (m->patch_x3) {                                      // split-precision patch embedding: fp16 product + e4m3 correction segments
-        RUN(sprc_im2row(images, v.rows, B, m->image, m->patch_size, m->patch_k_pad, SPRC_F16X3, st));
-        RUN(gemm(st, dt, SPRC_F32, P, D, m->patch_k_pad, v.rows, 2 * m->patch_k_pad, m->patch, v.pout, D, SPRC_ACT_NONE, nullptr, 0, ID_MAP,
-                 ID_MAP, nullptr, 0, nullptr, 2 * m->patch_k_pad, 2 * m->patch_k_pad, patch_k));
-    } else {
-        RUN(sprc_im2row(images, v.rows, B, m->image, m->patch_size, m->patch_k_pad, dt, st));
-        RUN(gemm(st, dt, SPRC_F32, P, D, m->patch_k_pad, v.rows, m->patch_k_pad, m->patch, v.pout, D, SPRC_ACT_NONE, nullptr, 0, ID_MAP, ID_MAP,
-                 nullptr, 0, nullptr, 0, 0, patch_k));
-    }
+    // split-precision patch embedding (patch_x3): fp16 product + e4m3 correction segments, rows and weights twice as wide (fp16 units)
+    const int px = m->patch_x3 ? 2 : 1, k_pad = m->patch_k_pad;
+    RUN(sprc_im2row(images, v.rows, B, m->image, m->patch_size, k_pad, m->patch_x3 ? SPRC_F16X3 : dt, st));
+    RUN(Gemm(dt, SPRC_F32, P, D, k_pad, v.rows, px * k_pad, m->patch, v.pout, D).split(px * k_pad, m->patch_x3 ? 2 * k_pad : 0).k_alg(patch_k).run(st));
     RUN(sprc_vit_assemble(v.pout, m->cls, m->pos, v.x, B, T, D, st));
     if (m->has_ln_pre) RUN(lnorm(st, dt, M, D, v.x, m->ln_pre_w, m->ln_pre_b, m->ln_eps, v.x, nullptr));
     // ---- transformer blocks.  SPRC_VIT_STREAMS=2 runs the two halves of the batch on two streams (the caller's and one
@@ -410,44 +414,31 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
     SPRC_REQUIRE(!fp8 || (is16(dt) && D % 128 == 0 && F % 128 == 0), "sprc_vit_forward: the fp8 path needs a 16-bit model with width, mlp %% 128 == 0");
     SPRC_REQUIRE(!(fp8 && m->calib_amax), "sprc_vit_forward: calibrate on the 16-bit model, not on the fp8 one");
     float* calib = (is16(dt) && !fp8) ? m->calib_amax : nullptr;
+    // The block is written once over its three quantisable products (qkv, fc1, fc2).  A site is what differs there: the operand dtype
+    // its producer writes, the producer's scale (1 / a_scale) and the product's scales -- the compute dtype and no scales for a 16-bit site.
+    // fp8 ViT block: LN -> e4m3 operand (static scale), qkv / fc1 / fc2 on fp8 MFMA with per-channel weight scales,
+    // fc1's GELU output quantised in its epilogue; attention and proj stay bf16; residual stream / LN fp32.
+    // h (bf16-sized) holds the fp8 operand: half its bytes, leading dimension D bytes.
+    struct Site { int dt; float in_scale; Fp8Scales q; };
+    auto site = [&](bool on, const float* w_scale, float a_scale, float out_scale) {
+        return on ? Site{SPRC_FP8, 1.0f / a_scale, {w_scale, a_scale, out_scale}} : Site{dt, 0.f, {nullptr, 0.f, 0.f}};
+    };
     for (int l = 0; l < m->depth; ++l) {                    // enqueue layer by layer, alternating streams: both stay fed
         const sprc_vit_layer& L = m->layers[l];
         for (int i = 0; i < nparts; ++i) {
             const Part& q = parts[i];
-            if (fp8) {
-                // fp8 ViT block: LN -> e4m3 operand (static scale), qkv / fc1 / fc2 on fp8 MFMA with per-channel weight scales,
-                // fc1's GELU output quantised in its epilogue; attention and proj stay bf16; residual stream / LN fp32.
-                // h (bf16-sized) holds the fp8 operand: half its bytes, leading dimension D bytes.
-                const Fp8Scales s_qkv{L.qkv_ws, L.s_ln1, 0.f}, s_fc1{L.fc1_ws, L.s_ln2, 1.0f / L.s_mlp}, s_fc2{L.fc2_ws, L.s_mlp, 0.f};
-                if (fp8_qkv) {
-                    RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h, ID_MAP, 1.0f / L.s_ln1));
-                    RUN(gemm(q.ps, SPRC_FP8, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D, SPRC_ACT_NONE, nullptr, 0, ID_MAP, ID_MAP,
-                             nullptr, 0, &s_qkv));
-                } else {
-                    RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h));
-                    RUN(gemm(q.ps, dt, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D));
-                }
-                RUN(attn(q.ps, dt, q.Bp, m->heads, T, T, m->head_dim, q.qkv, 3 * D, q.qkv + D * es, 3 * D, q.qkv + 2 * D * es, 3 * D,
-                         q.ctx, D, nullptr, scale));
-                RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D, SPRC_ACT_NONE, q.x, D));
-                RUN(lnorm(q.ps, SPRC_FP8, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h, ID_MAP, 1.0f / L.s_ln2));
-                RUN(gemm(q.ps, SPRC_FP8, SPRC_FP8, q.Mp, F, D, q.h, D, L.fc1, q.mlp, F, m->act, nullptr, 0, ID_MAP, ID_MAP, nullptr, 0, &s_fc1));
-                RUN(gemm(q.ps, SPRC_FP8, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D, SPRC_ACT_NONE, q.x, D, ID_MAP, ID_MAP, q.scratch,
-                         scratch_bytes, &s_fc2));
-                continue;
-            }
-            RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h));
+            const Site qkv = site(fp8_qkv, L.qkv_ws, L.s_ln1, 0.f), fc2 = site(fp8, L.fc2_ws, L.s_mlp, 0.f),
+                       fc1 = site(fp8, L.fc1_ws, L.s_ln2, fc2.in_scale);
+            RUN(lnorm(q.ps, qkv.dt, q.Mp, D, q.x, L.ln1_w, L.ln1_b, m->ln_eps, nullptr, q.h, ID_MAP, qkv.in_scale));
             if (calib) RUN(sprc_absmax_16(q.h, (size_t)q.Mp * D, dt, calib + l * 3 + 0, q.ps));
-            RUN(gemm(q.ps, dt, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D));
-            RUN(attn(q.ps, dt, q.Bp, m->heads, T, T, m->head_dim, q.qkv, 3 * D, q.qkv + D * es, 3 * D, q.qkv + 2 * D * es, 3 * D,
-                     q.ctx, D, nullptr, scale));
-            RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D, SPRC_ACT_NONE, q.x, D));
-            RUN(lnorm(q.ps, dt, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h));
+            RUN(Gemm(qkv.dt, dt, q.Mp, 3 * D, D, q.h, D, L.qkv, q.qkv, 3 * D).fp8(qkv.q).run(q.ps));
+            RUN(Attn(dt, q.Bp, m->heads, T, m->head_dim, q.qkv, D, q.ctx, D, scale).run(q.ps));
+            RUN(Gemm(dt, SPRC_F32, q.Mp, D, D, q.ctx, D, L.proj, q.x, D).resid(q.x, D).run(q.ps));
+            RUN(lnorm(q.ps, fc1.dt, q.Mp, D, q.x, L.ln2_w, L.ln2_b, m->ln_eps, nullptr, q.h, ID_MAP, fc1.in_scale));
             if (calib) RUN(sprc_absmax_16(q.h, (size_t)q.Mp * D, dt, calib + l * 3 + 1, q.ps));
-            RUN(gemm(q.ps, dt, dt, q.Mp, F, D, q.h, D, L.fc1, q.mlp, F, m->act));
+            RUN(Gemm(fc1.dt, fc2.dt, q.Mp, F, D, q.h, D, L.fc1, q.mlp, F).act(m->act).fp8(fc1.q).run(q.ps));
             if (calib) RUN(sprc_absmax_16(q.mlp, (size_t)q.Mp * F, dt, calib + l * 3 + 2, q.ps));
-            RUN(gemm(q.ps, dt, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D, SPRC_ACT_NONE, q.x, D, ID_MAP, ID_MAP, q.scratch,
-                     scratch_bytes));
+            RUN(Gemm(fc2.dt, SPRC_F32, q.Mp, D, F, q.mlp, F, L.fc2, q.x, D).resid(q.x, D).scratch(q.scratch, scratch_bytes).fp8(fc2.q).run(q.ps));
         }
     }
     if (m->pre_ln_out != nullptr) {
@@ -468,32 +459,18 @@ extern "C" int sprc_vit_forward(const sprc_vit_model* m, const float* images, in
 
 extern "C" int sprc_qformer_image(const sprc_qformer_model* m, const float* raw, int32_t B, float* feats, void* feats16,
                                   void* ws, size_t ws_bytes, sprc_stream s) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE(raw && feats && ws && B > 0, "sprc_qformer_image: bad arguments");
-    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "sprc_qformer_image: workspace must be 256-byte aligned");
+    const char* fn = "sprc_qformer_image";
     const int T = 257;
-    Bump b(ws, ws_bytes);
     QfBufs q;
-    qf_plan(m, B, T, b, q);
-    if (!b.ok) {
-        set_error("sprc_qformer_image: workspace too small (%zu bytes given)", ws_bytes);
-        return SPRC_EWORKSPACE;
-    }
+    RUN(check_qf(fn, m, raw && feats && ws && B > 0));
+    RUN(qf_carve(fn, m, B, T, true, ws, ws_bytes, q));
     hipStream_t st = (hipStream_t)s;
-    const int dt = m->dtype, Hd = m->hidden, Lq = m->num_query;
-    const int cm = m->x3_image;
+    const int Lq = m->num_query, cm = m->x3_image;
     RUN(qf_encode_kv(m, st, q.enc, q.kv, raw, B, T, cm));
-    const KvSrc kvs{q.kv, T, nullptr, nullptr, 0, nullptr, (int64_t)m->n_cross * 2 * Hd};
-    sprc_qformer_embed_args e;
-    memset(&e, 0, sizeof(e));
-    e.B = B; e.Lq = Lq; e.Lt = 0; e.hidden = Hd; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : dt;
-    e.query_embeds = m->query_tokens; e.q_bstride = 0;
-    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
-    e.y32 = q.h32; e.y16 = q.h16;
-    RUN(sprc_qformer_embed(&e, st));
+    const KvSrc kvs{q.kv, T, nullptr, nullptr, 0, nullptr, (int64_t)m->n_cross * 2 * m->hidden};
+    RUN(qf_embed(m, st, cm, B, Lq, 0, m->query_tokens, 0, nullptr, false, q.h32, q.h16));
     RUN(qf_stack(m, st, q, B, Lq, &kvs, nullptr, q.h32, q.h16, cm));
-    RUN(head(m, st, cm, B * Lq, q.h16, m->vision_proj, q.proj, ID_MAP));
-    return sprc_l2norm_rows(q.proj, m->embed_dim, feats, feats16, m->embed_dim, B * Lq, m->embed_dim, dt, st);
+    return qf_project(m, st, cm, q, B * Lq, q.h16, ID_MAP, m->vision_proj, feats, feats16);
 }
 
 // kv != nullptr: the K|V projections of the reference images are GIVEN (rows of an sprc_qformer_encode_kv output, query b reads row
@@ -502,44 +479,27 @@ static int qformer_fuse_impl(const sprc_qformer_model* m, const float* ref_embed
                              const int64_t* input_ids, const int64_t* attention_mask, int32_t B, float* fusion,
                              void* fusion16, const float* prompt_tokens, float* loss_align, void* ws, size_t ws_bytes, sprc_stream s,
                              const void* kv = nullptr, const int32_t* kv_index = nullptr) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE((ref_embeds || kv) && input_ids && attention_mask && fusion && ws && B > 0, "sprc_qformer_fuse: bad arguments");
-    SPRC_REQUIRE(enc_tokens == 257, "sprc_qformer_fuse: enc_tokens=%d (sprc_qformer_workspace_bytes plans for 257)", enc_tokens);
-    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "sprc_qformer_fuse: workspace must be 256-byte aligned");
-    Bump b(ws, ws_bytes);
+    const char* fn = "sprc_qformer_fuse";
     QfBufs q;
-    qf_plan(m, B, enc_tokens, b, q);
-    if (!b.ok) {
-        set_error("sprc_qformer_fuse: workspace too small (%zu bytes given)", ws_bytes);
-        return SPRC_EWORKSPACE;
-    }
+    RUN(check_qf(fn, m, (ref_embeds || kv) && input_ids && attention_mask && fusion && ws && B > 0));
+    SPRC_REQUIRE(enc_tokens == 257, "sprc_qformer_fuse: enc_tokens=%d (sprc_qformer_workspace_bytes plans for 257)", enc_tokens);
+    RUN(qf_carve(fn, m, B, enc_tokens, true, ws, ws_bytes, q));
     hipStream_t st = (hipStream_t)s;
-    const int dt = m->dtype, Hd = m->hidden, Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt;
+    const int Hd = m->hidden, Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt;
     const int cm = m->x3_fuse;
     if (kv == nullptr) RUN(qf_encode_kv(m, st, q.enc, q.kv, ref_embeds, B, enc_tokens, cm));
     const KvSrc kvs{kv != nullptr ? kv : q.kv, enc_tokens, kv != nullptr ? kv_index : nullptr, nullptr, 0, nullptr, (int64_t)m->n_cross * 2 * Hd};
     RUN(sprc_qformer_mask(attention_mask, q.mask, B, Lq, Lt, st));
-    sprc_qformer_embed_args e;
-    memset(&e, 0, sizeof(e));
-    e.B = B; e.Lq = Lq; e.Lt = Lt; e.hidden = Hd; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : dt; e.vocab = m->vocab;
-    e.input_ids = input_ids; e.word_emb = m->word_emb; e.pos_emb = m->pos_emb;
-    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
     // pass 1: learned query tokens + text, cross-attention to the reference image (align_prompt.py:332-339)
-    e.query_embeds = m->query_tokens; e.q_bstride = 0;
-    e.y32 = q.h32; e.y16 = q.h16;
-    RUN(sprc_qformer_embed(&e, st));
+    RUN(qf_embed(m, st, cm, B, Lq, Lt, m->query_tokens, 0, input_ids, false, q.h32, q.h16));
     RUN(qf_stack(m, st, q, B, S, &kvs, q.mask, q.h32, q.h16, cm, 0, Lq));       // read: the query rows
     if (loss_align != nullptr)                  // training: mse(mean fused query token, mean prompt token)  (align_prompt.py:192-193)
         RUN(sprc_align_mse(q.h32, (int64_t)S * Hd, Lq, Hd, prompt_tokens, B, loss_align, st));
     // pass 2: pass-1 query rows as query_embeds (re-LayerNormed by the embedding LN), no image (:341-346)
-    e.query_embeds = q.h32; e.q_bstride = (int64_t)S * Hd;
-    e.y32 = q.g32; e.y16 = q.g16;
-    RUN(sprc_qformer_embed(&e, st));
+    RUN(qf_embed(m, st, cm, B, Lq, Lt, q.h32, (int64_t)S * Hd, input_ids, false, q.g32, q.g16));
     RUN(qf_stack(m, st, q, B, S, nullptr, q.mask, q.g32, q.g16, cm, Lq, 1));     // read: the [CLS] row
     // fusion = normalize(text_proj(pass2[:, 32, :]))  (:348-350): row Lq of every sample
-    const sprc_rowmap cls_row = {1, S, Lq};
-    RUN(head(m, st, cm, B, q.g16, m->text_proj, q.proj, cls_row));
-    return sprc_l2norm_rows(q.proj, m->embed_dim, fusion, fusion16, m->embed_dim, B, m->embed_dim, dt, st);
+    return qf_project(m, st, cm, q, B, q.g16, sprc_rowmap{1, S, Lq}, m->text_proj, fusion, fusion16);
 }
 
 extern "C" int sprc_qformer_fuse_kv(const sprc_qformer_model* m, const void* kv, int32_t enc_tokens, const int32_t* kv_index,
@@ -569,60 +529,32 @@ extern "C" int sprc_qformer_fuse_train(const sprc_qformer_model* m, const float*
 extern "C" int sprc_qformer_text_only(const sprc_qformer_model* m, const float* prompt_tokens, const int64_t* input_ids,
                                       const int64_t* attention_mask, int32_t B, float* feat, void* feat16, void* ws,
                                       size_t ws_bytes, sprc_stream s) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE(prompt_tokens && input_ids && attention_mask && feat && ws && B > 0, "sprc_qformer_text_only: bad arguments");
-    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "sprc_qformer_text_only: workspace must be 256-byte aligned");
-    Bump b(ws, ws_bytes);
+    const char* fn = "sprc_qformer_text_only";
     QfBufs q;
-    qf_plan(m, B, 0, b, q, false);
-    if (!b.ok) {
-        set_error("sprc_qformer_text_only: workspace too small (%zu bytes given)", ws_bytes);
-        return SPRC_EWORKSPACE;
-    }
+    RUN(check_qf(fn, m, prompt_tokens && input_ids && attention_mask && feat && ws && B > 0));
+    RUN(qf_carve(fn, m, B, 0, false, ws, ws_bytes, q));
     hipStream_t st = (hipStream_t)s;
-    const int dt = m->dtype, Hd = m->hidden, Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt;
+    const int Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt, cm = m->x3_fuse;
     RUN(sprc_qformer_mask(attention_mask, q.mask, B, Lq, Lt, st));          // cat([ones(32), text mask]) as the reference passes it (:174-176)
-    sprc_qformer_embed_args e;
-    memset(&e, 0, sizeof(e));
-    const int cm = m->x3_fuse;
-    e.B = B; e.Lq = Lq; e.Lt = Lt; e.hidden = Hd; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : dt; e.vocab = m->vocab; e.no_img = 1;
-    e.input_ids = input_ids; e.word_emb = m->word_emb; e.pos_emb = m->pos_emb;
-    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
-    e.query_embeds = prompt_tokens; e.q_bstride = 0;
-    e.y32 = q.h32; e.y16 = q.h16;
-    RUN(sprc_qformer_embed(&e, st));
+    RUN(qf_embed(m, st, cm, B, Lq, Lt, prompt_tokens, 0, input_ids, true, q.h32, q.h16));
     RUN(qf_stack(m, st, q, B, S, nullptr, q.mask, q.h32, q.h16, cm, 0, 1));
-    const sprc_rowmap row0 = {1, S, 0};                                      // last_hidden_state[:, 0, :]  (:177-179)
-    RUN(head(m, st, cm, B, q.h16, m->text_proj, q.proj, row0));
-    return sprc_l2norm_rows(q.proj, m->embed_dim, feat, feat16, m->embed_dim, B, m->embed_dim, dt, st);
+    // last_hidden_state[:, 0, :]  (:177-179)
+    return qf_project(m, st, cm, q, B, q.h16, sprc_rowmap{1, S, 0}, m->text_proj, feat, feat16);
 }
 
 extern "C" int sprc_qformer_text(const sprc_qformer_model* m, const int64_t* input_ids, const int64_t* attention_mask, int32_t B,
                                  float* feat, void* feat16, void* ws, size_t ws_bytes, sprc_stream s) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE(input_ids && attention_mask && feat && ws && B > 0, "sprc_qformer_text: bad arguments");
-    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "sprc_qformer_text: workspace must be 256-byte aligned");
-    Bump b(ws, ws_bytes);
+    const char* fn = "sprc_qformer_text";
     QfBufs q;
-    qf_plan(m, B, 0, b, q, false);
-    if (!b.ok) {
-        set_error("sprc_qformer_text: workspace too small (%zu bytes given)", ws_bytes);
-        return SPRC_EWORKSPACE;
-    }
+    RUN(check_qf(fn, m, input_ids && attention_mask && feat && ws && B > 0));
+    RUN(qf_carve(fn, m, B, 0, false, ws, ws_bytes, q));
     hipStream_t st = (hipStream_t)s;
-    const int dt = m->dtype, Hd = m->hidden, Lt = m->max_txt, cm = m->x3_fuse;
+    const int Lt = m->max_txt, cm = m->x3_fuse;
     RUN(sprc_qformer_mask(attention_mask, q.mask, B, 0, Lt, st));              // (1 - mask) * -10000 over the Lt text keys (Qformer.py:806-807)
-    sprc_qformer_embed_args e;
-    memset(&e, 0, sizeof(e));
-    e.B = B; e.Lq = 0; e.Lt = Lt; e.hidden = Hd; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : dt; e.vocab = m->vocab;
-    e.input_ids = input_ids; e.word_emb = m->word_emb; e.pos_emb = m->pos_emb;
-    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
-    e.y32 = q.h32; e.y16 = q.h16;
-    RUN(sprc_qformer_embed(&e, st));
+    RUN(qf_embed(m, st, cm, B, 0, Lt, nullptr, 0, input_ids, false, q.h32, q.h16));
     RUN(qf_stack(m, st, q, B, Lt, nullptr, q.mask, q.h32, q.h16, cm, 0, 1));
-    const sprc_rowmap row0 = {1, Lt, 0};                                     // last_hidden_state[:, 0, :]  (rerank.py:388-390)
-    RUN(head(m, st, cm, B, q.h16, m->text_proj, q.proj, row0));
-    return sprc_l2norm_rows(q.proj, m->embed_dim, feat, feat16, m->embed_dim, B, m->embed_dim, dt, st);
+    // last_hidden_state[:, 0, :]  (rerank.py:388-390)
+    return qf_project(m, st, cm, q, B, q.h16, sprc_rowmap{1, Lt, 0}, m->text_proj, feat, feat16);
 }
 
 // ---- stage-2 rerank: blip2_qformer_cir_rerank.py:399-445 ------------------------------------------
@@ -633,8 +565,7 @@ extern "C" size_t sprc_qformer_kv_workspace_bytes(const sprc_qformer_model* m, i
 
 extern "C" int sprc_qformer_encode_kv(const sprc_qformer_model* m, const float* raw, int32_t B, int32_t tokens, void* kv,
                                       void* ws, size_t ws_bytes, sprc_stream s) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE(raw && kv && B > 0 && tokens > 0, "sprc_qformer_encode_kv: bad arguments");
+    RUN(check_qf("sprc_qformer_encode_kv", m, raw && kv && B > 0 && tokens > 0));
     SPRC_REQUIRE(!is16(m->dtype) || (ws && ((uintptr_t)ws % 256) == 0 && ws_bytes >= sprc_qformer_kv_workspace_bytes(m, B, tokens) - 512),
                  "sprc_qformer_encode_kv: workspace too small or misaligned");
     SPRC_REQUIRE(((uintptr_t)kv % 16) == 0, "sprc_qformer_encode_kv: kv must be 16-byte aligned");
@@ -652,29 +583,15 @@ extern "C" int sprc_qformer_itm(const sprc_qformer_model* m, const float* itm_w,
                                 int32_t tokens_a, const int32_t* index_a, const void* kv_b, int32_t tokens_b,
                                 const int32_t* index_b, const int64_t* input_ids, const int64_t* attention_mask, int32_t P,
                                 float* prob, void* ws, size_t ws_bytes, sprc_stream s) {
-    RUN(check_qf(m));
-    SPRC_REQUIRE(itm_w && itm_b && kv_a && kv_b && input_ids && attention_mask && prob && ws && P > 0, "sprc_qformer_itm: bad arguments");
-    SPRC_REQUIRE(tokens_a > 0 && tokens_b > 0, "sprc_qformer_itm: empty key segment");
-    SPRC_REQUIRE(((uintptr_t)ws % 256) == 0, "sprc_qformer_itm: workspace must be 256-byte aligned");
-    Bump b(ws, ws_bytes);
+    const char* fn = "sprc_qformer_itm";
     QfBufs q;
-    qf_plan(m, P, 0, b, q, false);
-    if (!b.ok) {
-        set_error("sprc_qformer_itm: workspace too small (%zu bytes given)", ws_bytes);
-        return SPRC_EWORKSPACE;
-    }
+    RUN(check_qf(fn, m, itm_w && itm_b && kv_a && kv_b && input_ids && attention_mask && prob && ws && P > 0));
+    SPRC_REQUIRE(tokens_a > 0 && tokens_b > 0, "sprc_qformer_itm: empty key segment");
+    RUN(qf_carve(fn, m, P, 0, false, ws, ws_bytes, q));
     hipStream_t st = (hipStream_t)s;
-    const int dt = m->dtype, Hd = m->hidden, Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt;
+    const int Hd = m->hidden, Lq = m->num_query, Lt = m->max_txt, S = Lq + Lt, cm = m->x3_fuse;
     RUN(sprc_qformer_mask(attention_mask, q.mask, P, Lq, Lt, st));
-    sprc_qformer_embed_args e;
-    memset(&e, 0, sizeof(e));
-    const int cm = m->x3_fuse;
-    e.B = P; e.Lq = Lq; e.Lt = Lt; e.hidden = Hd; e.out_dtype = x3_layouts(cm).ln ? SPRC_F16X3 : dt; e.vocab = m->vocab;
-    e.input_ids = input_ids; e.word_emb = m->word_emb; e.pos_emb = m->pos_emb;
-    e.gamma = m->emb_ln_w; e.beta = m->emb_ln_b; e.eps = m->ln_eps;
-    e.query_embeds = m->query_tokens; e.q_bstride = 0;
-    e.y32 = q.h32; e.y16 = q.h16;
-    RUN(sprc_qformer_embed(&e, st));
+    RUN(qf_embed(m, st, cm, P, Lq, Lt, m->query_tokens, 0, input_ids, false, q.h32, q.h16));
     // one Q-Former pass in call shape (ii) over cat(reference, candidate) tokens (:430-437)
     const KvSrc kvs{kv_a, tokens_a, index_a, kv_b, tokens_b, index_b, (int64_t)m->n_cross * 2 * Hd};
     RUN(qf_stack(m, st, q, P, S, &kvs, q.mask, q.h32, q.h16, cm, 0, Lq));      // read: the query rows (itm_head)

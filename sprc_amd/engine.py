@@ -484,15 +484,37 @@ class Engine:
         return amax.cpu()
 
     # ---- workspaces ------------------------------------------------------------------------
-    def _workspace(self, kind: str, B: int) -> torch.Tensor:
-        is_vit = kind.startswith("vit")                                                                         # "vit", "vit#1", "qf", "qf_image"
-        fn = self.lib.sprc_vit_workspace_bytes if is_vit else self.lib.sprc_qformer_workspace_bytes
-        need = int(fn(C.byref(self.vit if is_vit else self.qf), B))
+    _WS_BYTES = {"vit": "sprc_vit_workspace_bytes", "qf": "sprc_qformer_workspace_bytes", "kv": "sprc_qformer_kv_workspace_bytes",
+                 "itm": "sprc_qformer_itm_workspace_bytes"}
+
+    def _workspace(self, kind: str, *dims: int) -> torch.Tensor:
+        """The cached workspace `kind` ("vit", "vit#1", "qf", "qf_image", "kv", "itm"), grown to what a call of `dims` needs:
+        the batch, for "kv" (batch, tokens).  The name up to '#' or '_' selects the C sizing function."""
+        family = kind.split("#")[0].split("_")[0]
+        need = int(getattr(self.lib, self._WS_BYTES[family])(C.byref(self.vit if family == "vit" else self.qf), *dims))
         ws = self._ws.get(kind)
         if ws is None or ws.numel() < need:
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._ws[kind] = ws
         return ws
+
+    def _chunks(self, B: int, ws_kind: str, *ws_dims: int, step: Optional[int] = None):
+        """The batch in pieces of at most `step` (default max_batch): yields (first row, rows, workspace of `ws_kind` for them)."""
+        step = self.max_batch if step is None else step
+        for s in range(0, B, step):
+            n = min(step, B - s)
+            yield s, n, self._workspace(ws_kind, n, *ws_dims)
+
+    def _ids_mask(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, B: Optional[int] = None, check_range: bool = False):
+        """-> (input_ids, attention_mask) as contiguous int64 on the device.  B: the batch they must describe, [B, max_txt_len];
+        check_range: refuse host-resident ids outside the vocabulary (device-resident ids are clamped by the kernel: no host sync)."""
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
+        if B is not None and (ids.shape != (B, self.cfg.max_txt_len) or mask.shape != ids.shape):
+            raise ValueError(f"input_ids/attention_mask must be [{B},{self.cfg.max_txt_len}]")
+        if check_range and not input_ids.is_cuda and (int(input_ids.min()) < 0 or int(input_ids.max()) >= self.cfg.qformer.vocab):
+            raise IndexError("token id out of range")
+        return ids, mask
 
     # ---- forward passes ----------------------------------------------------------------------
     @_on_device
@@ -509,9 +531,7 @@ class Engine:
         if pre_ln_out is not None:
             assert pre_ln_out.dtype == torch.float32 and pre_ln_out.is_contiguous() and pre_ln_out.numel() == B * v.tokens * v.width
         try:
-            for s in range(0, B, self.max_batch):
-                n = min(self.max_batch, B - s)
-                ws = self._workspace("vit" if slot == 0 else f"vit#{slot}", n)
+            for s, n, ws in self._chunks(B, "vit" if slot == 0 else f"vit#{slot}"):
                 if pre_ln_out is not None:
                     self.vit.pre_ln_out = pre_ln_out.data_ptr() + s * v.tokens * v.width * 4
                 L.check(self.lib.sprc_vit_forward(C.byref(self.vit), images[s:s + n].data_ptr(), n, raw[s:s + n].data_ptr(),
@@ -529,9 +549,7 @@ class Engine:
         B, E, Lq = raw.shape[0], self.cfg.embed_dim, self.cfg.qformer.num_query
         feats = torch.empty((B, Lq, E), dtype=torch.float32, device=self.device)
         f16 = torch.empty((B, Lq, E), dtype=self.tdt, device=self.device) if self.is16 else None
-        for s in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - s)
-            ws = self._workspace("qf_image", n)          # its own workspace: the image pass may run on a side stream beside a fusion pass
+        for s, n, ws in self._chunks(B, "qf_image"):   # its own workspace: the image pass may run on a side stream beside a fusion pass
             L.check(self.lib.sprc_qformer_image(C.byref(self.qf), raw[s:s + n].data_ptr(), n, feats[s:s + n].data_ptr(),
                                                 None if f16 is None else f16[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(),
                                                 _stream(self.device)), "sprc_qformer_image")
@@ -543,18 +561,11 @@ class Engine:
         ref = ref_embeds.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(ref.shape[1:]) != (self.cfg.vit.tokens, self.cfg.vit.width):
             raise ValueError(f"reference embeddings must be [B, {self.cfg.vit.tokens}, {self.cfg.vit.width}], got {tuple(ref.shape)}")
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
         B, E = ref.shape[0], self.cfg.embed_dim
-        if ids.shape != (B, self.cfg.max_txt_len) or mask.shape != ids.shape:
-            raise ValueError(f"input_ids/attention_mask must be [{B},{self.cfg.max_txt_len}]")
-        if not input_ids.is_cuda and (int(input_ids.min()) < 0 or int(input_ids.max()) >= self.cfg.qformer.vocab):
-            raise IndexError("token id out of range")       # device-resident ids are clamped by the kernel (no host sync)
+        ids, mask = self._ids_mask(input_ids, attention_mask, B, check_range=True)
         fusion = torch.empty((B, E), dtype=torch.float32, device=self.device)
         f16 = torch.empty((B, E), dtype=self.tdt, device=self.device) if self.is16 else None
-        for s in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - s)
-            ws = self._workspace("qf", n)
+        for s, n, ws in self._chunks(B, "qf"):
             L.check(self.lib.sprc_qformer_fuse(C.byref(self.qf), ref[s:s + n].data_ptr(), ref.shape[1], ids[s:s + n].data_ptr(),
                                                mask[s:s + n].data_ptr(), n, fusion[s:s + n].data_ptr(),
                                                None if f16 is None else f16[s:s + n].data_ptr(), ws.data_ptr(), ws.numel(),
@@ -569,18 +580,13 @@ class Engine:
         if not self.is16 or kv.dtype != self.tdt or kv.dim() != 3 or kv.shape[1:] != (self.cfg.vit.tokens, self.kv_width) or not kv.is_contiguous():
             raise ValueError("kv must be a contiguous Engine.encode_kv output [n, tokens, kv_width] of a 16-bit engine")
         idx = kv_index.to(device=self.device, dtype=torch.int32).contiguous()
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
         B, E = idx.shape[0], self.cfg.embed_dim
-        if ids.shape != (B, self.cfg.max_txt_len) or mask.shape != ids.shape:
-            raise ValueError(f"input_ids/attention_mask must be [{B},{self.cfg.max_txt_len}]")
+        ids, mask = self._ids_mask(input_ids, attention_mask, B)
         if B and (int(idx.min()) < 0 or int(idx.max()) >= kv.shape[0]):
             raise IndexError("kv_index out of range")
         fusion = torch.empty((B, E), dtype=torch.float32, device=self.device)
         f16 = torch.empty((B, E), dtype=self.tdt, device=self.device)
-        for s in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - s)
-            ws = self._workspace("qf", n)
+        for s, n, ws in self._chunks(B, "qf"):
             L.check(self.lib.sprc_qformer_fuse_kv(C.byref(self.qf), kv.data_ptr(), kv.shape[1], idx[s:s + n].data_ptr(), ids[s:s + n].data_ptr(),
                                                   mask[s:s + n].data_ptr(), n, fusion[s:s + n].data_ptr(), f16[s:s + n].data_ptr(),
                                                   ws.data_ptr(), ws.numel(), _stream(self.device)), "sprc_qformer_fuse_kv")
@@ -590,17 +596,10 @@ class Engine:
     def qformer_text(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         """feat[B,E] fp32 (unit rows) = normalize(text_proj(Qformer(text)[:, 0])): the Q-Former as a plain text encoder -- the
         stage-1 query feature of the rerank model class (blip2_qformer_cir_rerank.py:373-390)."""
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
-        B = ids.shape[0]
-        if ids.shape != (B, self.cfg.max_txt_len) or mask.shape != ids.shape:
-            raise ValueError(f"input_ids/attention_mask must be [{B},{self.cfg.max_txt_len}]")
-        if not input_ids.is_cuda and (int(input_ids.min()) < 0 or int(input_ids.max()) >= self.cfg.qformer.vocab):
-            raise IndexError("token id out of range")
+        B = input_ids.shape[0]
+        ids, mask = self._ids_mask(input_ids, attention_mask, B, check_range=True)
         feat = torch.empty((B, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
-        for s in range(0, B, self.max_batch):
-            n = min(self.max_batch, B - s)
-            ws = self._workspace("qf", n)
+        for s, n, ws in self._chunks(B, "qf"):
             L.check(self.lib.sprc_qformer_text(C.byref(self.qf), ids[s:s + n].data_ptr(), mask[s:s + n].data_ptr(), n,
                                                feat[s:s + n].data_ptr(), None, ws.data_ptr(), ws.numel(), _stream(self.device)),
                     "sprc_qformer_text")
@@ -619,13 +618,7 @@ class Engine:
         if D != self.cfg.vit.width:
             raise ValueError(f"raw embeddings must be [B, tokens, {self.cfg.vit.width}]")
         kv = out if out is not None else torch.empty((B, T, self.kv_width), dtype=self.tdt, device=self.device)
-        step = max(1, min(self.max_batch, 256))
-        for s in range(0, B, step):
-            n = min(step, B - s)
-            need = int(self.lib.sprc_qformer_kv_workspace_bytes(C.byref(self.qf), n, T))
-            ws = self._ws.get("kv")
-            if ws is None or ws.numel() < need:
-                ws = self._ws["kv"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        for s, n, ws in self._chunks(B, "kv", T, step=max(1, min(self.max_batch, 256))):
             L.check(self.lib.sprc_qformer_encode_kv(C.byref(self.qf), raw[s:s + n].data_ptr(), n, T, kv[s:s + n].data_ptr(),
                                                     ws.data_ptr(), ws.numel(), _stream(self.device)), "sprc_qformer_encode_kv")
         return kv
@@ -638,8 +631,7 @@ class Engine:
             raise L.SprcError("the state dict has no itm_head.*: stage-2 rerank needs the rerank checkpoint's ITM head")
         ia = index_a.to(device=self.device, dtype=torch.int32).contiguous()
         ib = index_b.to(device=self.device, dtype=torch.int32).contiguous()
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
+        ids, mask = self._ids_mask(input_ids, attention_mask)
         P = ia.shape[0]
         if ib.shape[0] != P or ids.shape != (P, self.cfg.max_txt_len) or mask.shape != ids.shape:
             raise ValueError("index_a / index_b / input_ids / attention_mask must describe the same P pairs")
@@ -649,12 +641,7 @@ class Engine:
         if P and (int(ia.max()) >= kv_a.shape[0] or int(ib.max()) >= kv_b.shape[0] or int(ia.min()) < 0 or int(ib.min()) < 0):
             raise IndexError("pair index out of range")
         prob = torch.empty((P,), dtype=torch.float32, device=self.device)
-        for s in range(0, P, self.max_batch):
-            n = min(self.max_batch, P - s)
-            need = int(self.lib.sprc_qformer_itm_workspace_bytes(C.byref(self.qf), n))
-            ws = self._ws.get("itm")
-            if ws is None or ws.numel() < need:
-                ws = self._ws["itm"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        for s, n, ws in self._chunks(P, "itm"):
             L.check(self.lib.sprc_qformer_itm(C.byref(self.qf), self.itm_w.data_ptr(), self.itm_b.data_ptr(),
                                               kv_a.data_ptr(), kv_a.shape[1], ia[s:s + n].data_ptr(),
                                               kv_b.data_ptr(), kv_b.shape[1], ib[s:s + n].data_ptr(),
@@ -674,8 +661,7 @@ class Engine:
         B = image.shape[0]
         if B > self.max_batch:
             raise ValueError(f"batch {B} > max_batch {self.max_batch}")
-        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
+        ids, mask = self._ids_mask(input_ids, attention_mask)
         raw_ref, raw_tgt = self.vit_forward(image), self.vit_forward(target)
         target_feats, _ = self.qformer_image(raw_tgt)
         E_ = self.cfg.embed_dim
