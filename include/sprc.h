@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SPRC_ABI_VERSION 7
+#define SPRC_ABI_VERSION 8
 
 enum { SPRC_OK = 0, SPRC_EINVAL = -1, SPRC_ELAUNCH = -2, SPRC_EWORKSPACE = -3, SPRC_EUNSUPPORTED = -4 };
 enum { SPRC_F32 = 0, SPRC_BF16 = 1,
@@ -252,6 +252,29 @@ int sprc_sim_max(const void* fusion, const void* feats, float* sim, int64_t ld_s
  * 1 <= k <= 64. */
 int sprc_topk(const float* sim, int64_t ld, const int32_t* gidx, int32_t idx_base,
               int32_t nq, int32_t N, int32_t k, float* out_sim, int32_t* out_idx, sprc_stream s);
+
+/* sprc_topk for 1 <= k <= 256, with an optional left-out column (ABI 8).  The same contract: keys
+ * (dist_bits(sim[n]) << 32) | id ascending with id = gidx[n] or n + idx_base, every comparison an integer comparison on the
+ * 64-bit key, NaN last, unused slots sim = -inf / idx = -1; the result does not depend on how the row is cut into steps.
+ *   skip  DEVICE int32 [nq] or NULL: column POSITION 0 <= skip[q] < N of row q is left out of the order (how the stage-2
+ *         validation removes the reference image before it takes the first 200, validate_blip_rerank.py:189-193,206);
+ *         a negative value leaves nothing out.
+ * For k <= 64 and skip == NULL the outputs are bit-identical to sprc_topk's.  k outside 1..256, N < 1 or ld < N is an error. */
+int sprc_topk_wide(const float* sim, int64_t ld, const int32_t* gidx, int32_t idx_base, const int32_t* skip,
+                   int32_t nq, int32_t N, int32_t k, float* out_sim, int32_t* out_idx, sprc_stream s);
+
+/* Stage-2 re-ordering (ABI 8; validate_blip_rerank.py:63-70, :212-219; cirr_test_submission.py:103-110).
+ *   cand  DEVICE int32 [nq,T], 1 <= T <= 256: gallery indices in stage-1 order; entries < 0 are padding.
+ *   prob  DEVICE fp32 [nq,T]: the stage-2 P(match) of every candidate.
+ *   out_idx [nq,T]: cand[q,:] sorted by the key (dist_bits(prob), stage-1 position) ascending, i.e. by a STABLE argsort of
+ *         fl32(1 - P); padding follows every real candidate (a NaN one included) and stays -1, whatever its prob.
+ *   listed, listed_rank  DEVICE int32 [nq,L], 0 <= L <= 16 (NULL allowed when L == 0); out_rank [nq,L]:
+ *         out_rank[q,l] = the new position of listed[q,l] when it is one of row q's candidates, listed_rank[q,l] otherwise
+ *         (an item beyond the first T keeps its stage-1 place), -1 when listed[q,l] < 0.  Two equal candidates in one row
+ *         are UNDEFINED for out_rank. */
+int sprc_rerank_order(const int32_t* cand, const float* prob, int32_t nq, int32_t T,
+                      const int32_t* listed, const int32_t* listed_rank, int32_t L,
+                      int32_t* out_idx, int32_t* out_rank, sprc_stream s);
 
 /* rank[q,l] = #{ n : (d[q,n], n) < (d[q,t], t) },  t = listed[q,l]  (-1 where t < 0): the position
  * of gallery item t in the stable order, without sorting (exact Recall@K for any K). */

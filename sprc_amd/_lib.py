@@ -14,7 +14,7 @@ LIB_PATH = Path(os.environ.get("SPRC_LIB_PATH") or (Path(__file__).resolve().par
 
 SPRC_F16X3 = 4                                        # storage layout of split-precision activations: rows [hi fp16 | lo e4m3 | hi e4m3] (sprc.h)
 SPRC_F32, SPRC_BF16, SPRC_F16, SPRC_FP8 = 0, 1, 2, 3   # F16: IEEE half (compute dtype since ABI 3); FP8: OCP e4m3fn operands
-ABI_VERSION = 7
+ABI_VERSION = 8
 ACT_NONE, ACT_GELU, ACT_QUICKGELU = 0, 1, 2
 FP8_ALL, FP8_MLP = 1, 2                               # sprc_vit_model.fp8: qkv + fc1 + fc2, or fc1 + fc2 only, on e4m3fn operands
 DTYPES = {"fp32": SPRC_F32, "f32": SPRC_F32, "bf16": SPRC_BF16, "fp16": SPRC_F16, "f16": SPRC_F16,
@@ -135,7 +135,9 @@ SIGNATURES = {
     "sprc_qformer_mask": (i32, [vp, vp, i32, i32, i32, vp]),
     "sprc_sim_max": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "sprc_topk": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "sprc_topk_wide": (i32, [vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
     "sprc_rank_of": (i32, [vp, i64, vp, i32, i32, i32, vp, vp]),
+    "sprc_rerank_order": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
     "sprc_ap_at_k": (i32, [vp, i64, vp, i32, i32, i32, C.POINTER(i32), i32, vp, vp, vp]),
     "sprc_vit_workspace_bytes": (sz, [C.POINTER(VitModel), i32]),
     "sprc_qformer_workspace_bytes": (sz, [C.POINTER(QformerModel), i32]),

@@ -4,7 +4,10 @@
 Entry point with the reference's flags and printed JSON keys (src/blip_validate.py:103-155), running the
 retrieval path on the MI355X HIP engine.  Extra flag: --dtype (bf16 | fp32).  `--dataset CIRCO [--circo-path P]` has no
 counterpart in the reference's script (it ships the CIRCO dataset class without an evaluator): mAP@K and Recall@K for
-K in {5, 10, 25, 50} on the val split.
+K in {5, 10, 25, 50} on the val split.  `--rerank true [--rerank-top N]` (CIRR / fashionIQ, `--blip-model-name
+blip2_cir_rerank`): the two-stage validation of the reference's src/validate_blip_rerank.py -- the first 200 (CIRR, reference image
+removed) / 40 (FashionIQ) of every query are re-scored with `inference_rerank` and the same metric lines are printed for the
+re-ordered list; single-process only.
 """
 from __future__ import annotations
 
@@ -16,8 +19,8 @@ from statistics import geometric_mean, harmonic_mean, mean
 
 import torch
 
-from .harness import (circo_reference_ids, compute_circo_val_metrics, compute_cirr_val_metrics, compute_fiq_val_metrics,
-                      extract_index_blip_features)
+from .harness import (circo_reference_ids, compute_circo_val_metrics, compute_cirr_val_metrics, compute_cirr_val_metrics_rerank,
+                      compute_fiq_val_metrics, compute_fiq_val_metrics_rerank, extract_index_blip_features)
 from .index import load_index, save_index
 from .model import load_model_and_preprocess
 
@@ -133,9 +136,18 @@ def _warn_index_cache_ignored(index_cache):
               file=sys.stderr)
 
 
+def _refuse_sharded_rerank(rerank: bool):
+    """The stage-2 rerank is not sharded: every rank would encode the whole gallery and rerank every pair (as
+    cirr_test_submission refuses it)."""
+    if rerank and _sharded():
+        raise SystemExit("blip_validate: --rerank runs on one process (launch without torchrun); the sharded path covers the "
+                         "stage-1 validation only")
+
+
 def blip_validate_cirr(blip_model_name, backbone, blip_model_path, dtype="fp16", index_cache=None, gpu_preprocess=False,
-                       vit_depth=None, reuse_reference_kv=False):
+                       vit_depth=None, reuse_reference_kv=False, rerank=False, rerank_top=None):
     from .data_utils import CIRRDataset
+    _refuse_sharded_rerank(rerank)
     model, txt = _load(blip_model_name, backbone, blip_model_path, dtype, vit_depth)
     preprocess, workers = _preprocess(gpu_preprocess, model.device)
     relative_val = CIRRDataset("val", "relative", preprocess)
@@ -146,7 +158,10 @@ def blip_validate_cirr(blip_model_name, backbone, blip_model_path, dtype="fp16",
         r = compute_cirr_val_metrics_sharded(relative_val, classic_val, model, txt, num_workers=workers)
     else:
         feats, names = _gallery(classic_val, model, index_cache, "cirr-val", backbone, dtype, workers)
-        r = compute_cirr_val_metrics(relative_val, model, feats, names, txt, reuse_reference_kv=reuse_reference_kv and dtype != "fp32")
+        if rerank:                     # validate_blip_rerank.py:165-248
+            r = compute_cirr_val_metrics_rerank(relative_val, model, feats, names, txt, **({"top": rerank_top} if rerank_top else {}))
+        else:
+            r = compute_cirr_val_metrics(relative_val, model, feats, names, txt, reuse_reference_kv=reuse_reference_kv and dtype != "fp32")
     g1, g2, g3, r1, r5, r10, r50 = r
     out = {"group_recall_at1": g1, "group_recall_at2": g2, "group_recall_at3": g3, "recall_at1": r1, "recall_at5": r5,
            "recall_at10": r10, "recall_at50": r50, "mean(R@5+R_s@1)": (g1 + r5) / 2, "arithmetic_mean": mean(r),
@@ -157,9 +172,10 @@ def blip_validate_cirr(blip_model_name, backbone, blip_model_path, dtype="fp16",
 
 
 def blip_validate_fiq(val_dress_types, blip_model_name, backbone, model_path, dtype="fp16", index_cache=None, gpu_preprocess=False,
-                      vit_depth=None):
+                      vit_depth=None, rerank=False, rerank_top=None):
     """FashionIQ evaluation (the reference calls this `clip_finetune_fiq`, blip_validate.py:26-98)."""
     from .data_utils import FashionIQDataset
+    _refuse_sharded_rerank(rerank)
     model, txt = _load(blip_model_name, backbone, model_path, dtype, vit_depth)
     model.eval()
     preprocess, workers = _preprocess(gpu_preprocess, model.device)
@@ -172,7 +188,10 @@ def blip_validate_fiq(val_dress_types, blip_model_name, backbone, model_path, dt
             r10, r50 = compute_fiq_val_metrics_sharded(relative, classic, model, txt, num_workers=workers)
         else:
             feats, names = _gallery(classic, model, index_cache, f"fiq-val-{d}", backbone, dtype, workers)
-            r10, r50 = compute_fiq_val_metrics(relative, model, feats, names, txt)
+            if rerank:                 # validate_blip_rerank.py:23-83
+                r10, r50 = compute_fiq_val_metrics_rerank(relative, model, feats, names, txt, **({"top": rerank_top} if rerank_top else {}))
+            else:
+                r10, r50 = compute_fiq_val_metrics(relative, model, feats, names, txt)
         r10s.append(r10)
         r50s.append(r50)
         torch.cuda.empty_cache()
@@ -225,18 +244,24 @@ def main(argv=None):
     p.add_argument("--gpu-preprocess", action="store_true", help="pad / bicubic resize / crop / normalise on the GPU (bit-identical to the PIL transform)")
     p.add_argument("--reuse-reference-kv", action="store_true", help="CIRR / CIRCO: project each distinct reference image to the Q-Former's cross-attention "
                    "K|V once instead of once per query (same scores; single-process, 16-bit engines)")
+    p.add_argument("--rerank", type=lambda v: str(v).lower() in ("yes", "true", "t", "y", "1"), default=False,
+                   help="CIRR / fashionIQ: two-stage validation (src/validate_blip_rerank.py) -- re-score every query's first candidates "
+                   "with the ITM head (--blip-model-name blip2_cir_rerank); single-process")
+    p.add_argument("--rerank-top", type=int, default=None, help="candidates re-scored per query (default: 200 for CIRR, 40 for fashionIQ; at most 256)")
     p.add_argument("--vit-depth", type=int, default=None, help="truncate the ViT to N blocks (entry-point smoke tests only)")
     a = p.parse_args(argv)
     if a.dataset.lower() not in ("fashioniq", "cirr", "circo"):
         raise ValueError("Dataset should be 'CIRR', 'FashionIQ' or 'CIRCO'")
     if a.dataset.lower() == "circo":
+        if a.rerank:
+            raise SystemExit("blip_validate: --rerank covers CIRR and fashionIQ (the reference has no two-stage CIRCO validation)")
         return blip_validate_circo(a.blip_model_name, a.backbone, a.model_path, a.dtype, a.index_cache, a.gpu_preprocess, a.vit_depth,
                                    reuse_reference_kv=a.reuse_reference_kv, circo_path=a.circo_path)
     if a.dataset.lower() == "cirr":
         return blip_validate_cirr(a.blip_model_name, a.backbone, a.model_path, a.dtype, a.index_cache, a.gpu_preprocess, a.vit_depth,
-                                  reuse_reference_kv=a.reuse_reference_kv)
+                                  reuse_reference_kv=a.reuse_reference_kv, rerank=a.rerank, rerank_top=a.rerank_top)
     return blip_validate_fiq(["dress", "toptee", "shirt"], a.blip_model_name, a.backbone, a.model_path, a.dtype, a.index_cache,
-                             a.gpu_preprocess, a.vit_depth)
+                             a.gpu_preprocess, a.vit_depth, rerank=a.rerank, rerank_top=a.rerank_top)
 
 
 if __name__ == "__main__":

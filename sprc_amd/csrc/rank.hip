@@ -15,6 +15,11 @@
 // sprc_rank_of: position of listed gallery items in that order by counting smaller keys (no sort).
 // sprc_ap_at_k: average precision at K over up to 32 ground truths per query (the CIRCO protocol): the ranks of all ground
 // truths from ONE counting pass over the row, then AP@K in fp64 from those ranks, summed in ascending-rank order.
+// sprc_topk_wide: top-k for k up to 256 with an optional left-out column (the stage-2 validation takes the first 200 of the
+// reference-less order): a running top-256 one key per THREAD, a 256-entry staging buffer in LDS fed by ballots, and a 512-key
+// bitonic sort (shuffles inside a wave, LDS between waves) whenever staging fills.
+// sprc_rerank_order: the stage-2 re-ordering of up to 256 candidates per query by (dist_bits(P), stage-1 position), and the new
+// places of up to 16 listed items, with the same sorting network.
 #include "common.hpp"
 
 namespace sprc {
@@ -118,6 +123,173 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sim
             out_sim[q * k + lane] = ok ? row[top.pos] : -INFINITY;
         }
     }
+}
+
+// Bitonic sort, ascending, of 256*E keys held E per thread by one 256-thread workgroup: item e of thread t is element t + 256*e.
+// A compare-exchange distance below 64 stays inside a wave (cmpxchg: shuffles), 64 and 128 go through the LDS exchange arrays
+// xk / xp (256*E entries each, two barriers per exchange), 256 is between a thread's own two items.  Every branch below is
+// decided by k, j and E alone, so the whole workgroup reaches the same barriers.
+template <int E>
+__device__ __forceinline__ void block_bitonic_sort(Item (&it)[E], int tid, uint64_t* xk, uint32_t* xp) {
+    const int lane = tid & 63;
+#pragma unroll
+    for (int k = 2; k <= 256 * E; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (j == 256) {                                  // E == 2, k == 512: ascending over the whole sequence
+                if (it[E - 1].key < it[0].key) {
+                    const Item t = it[0];
+                    it[0] = it[E - 1];
+                    it[E - 1] = t;
+                }
+            } else if (j >= 64) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    xk[tid + 256 * e] = it[e].key;
+                    xp[tid + 256 * e] = it[e].pos;
+                }
+                __syncthreads();
+                Item o[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    o[e].key = xk[(tid ^ j) + 256 * e];
+                    o[e].pos = xp[(tid ^ j) + 256 * e];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const bool keep_min = (((tid + 256 * e) & k) == 0) == ((tid & j) == 0);
+                    const bool take = keep_min ? (o[e].key < it[e].key) : (o[e].key > it[e].key);
+                    if (take) it[e] = o[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; ++e) cmpxchg(it[e], lane, j, (((tid + 256 * e) & k) == 0) == ((tid & j) == 0));
+            }
+        }
+    }
+}
+
+// One 256-thread workgroup per row; the row is read from HBM once, 256 elements per step (the next step's element is loaded
+// before this step's barrier).  Thread t keeps key t of the running top-256 (sorted ascending across the workgroup); `thr` is
+// its k-th key, ~0 until k keys have been seen.  A step ballots the keys below thr, the four wave counts meet in LDS (one
+// barrier per step, the count slots alternate), and the passing keys are appended to the 256-entry staging buffer.  When they
+// would not fit, and at the end of the row, top and staging are sorted as one 512-key sequence and the low half is the new
+// top.  A key at or above thr can never be among the k smallest, whatever arrives later, and everything else reaches the
+// sort: the result is the k smallest 64-bit keys of the row, however the row is cut into steps.  After the first steps
+// almost nothing passes and a step costs its load, one ballot and one barrier.
+__global__ __launch_bounds__(256) void topk_wide_kernel(const float* __restrict__ sim, int64_t ld, const int32_t* __restrict__ gidx,
+                                                        int idx_base, const int32_t* __restrict__ skip, int N, int k,
+                                                        float* __restrict__ out_sim, int32_t* __restrict__ out_idx) {
+    __shared__ uint64_t s_xk[512];
+    __shared__ uint32_t s_xp[512];
+    __shared__ uint64_t s_sk[256];         // staging
+    __shared__ uint32_t s_sp[256];
+    __shared__ uint64_t s_thr;
+    __shared__ int s_wcnt[3][4];           // [0], [1]: the steps' counts, alternating; [2]: the recount after a sort
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const float* row = sim + q * ld;
+    const int32_t* grow = gidx ? gidx + q * (int64_t)N : nullptr;
+    const int skipc = skip ? skip[q] : -1;
+
+    Item top[2];                           // [0]: this thread's key of the running top-256; [1]: its staging key during a sort
+    top[0].key = ~0ull;
+    top[0].pos = 0xffffffffu;
+    uint64_t thr = ~0ull;
+    int nstage = 0;                        // the same in every thread
+
+    auto flush = [&]() {                   // reached by the whole workgroup, after a barrier that follows the last staging write
+        top[1].key = tid < nstage ? s_sk[tid] : ~0ull;
+        top[1].pos = tid < nstage ? s_sp[tid] : 0xffffffffu;
+        block_bitonic_sort<2>(top, tid, s_xk, s_xp);     // (its barriers also separate the staging reads above from later appends)
+        if (tid == k - 1) s_thr = top[0].key;
+        __syncthreads();
+        thr = s_thr;
+        nstage = 0;
+    };
+
+    const int nsteps = (N + 255) >> 8;
+    float v = tid < N ? row[tid] : 0.0f;
+    for (int c = 0; c < nsteps; ++c) {
+        const int n = c * 256 + tid;
+        const float vn = n + 256 < N ? row[n + 256] : 0.0f;
+        uint64_t key = ~0ull;
+        if (n < N && n != skipc) {
+            const uint32_t id = grow ? (uint32_t)grow[n] : (uint32_t)(n + idx_base);
+            key = ((uint64_t)dist_bits(v) << 32) | id;
+        }
+        v = vn;
+        bool pass = key < thr;
+        uint64_t bal = __ballot(pass);
+        if (lane == 0) s_wcnt[c & 1][wave] = __popcll(bal);
+        __syncthreads();
+        int w0 = s_wcnt[c & 1][0], w1 = s_wcnt[c & 1][1], w2 = s_wcnt[c & 1][2], w3 = s_wcnt[c & 1][3];
+        if (w0 + w1 + w2 + w3 == 0) continue;
+        if (nstage + w0 + w1 + w2 + w3 > 256) {
+            flush();
+            pass = key < thr;              // a subset of what passed before: at most 256 keys, and staging is empty
+            bal = __ballot(pass);
+            if (lane == 0) s_wcnt[2][wave] = __popcll(bal);
+            __syncthreads();
+            w0 = s_wcnt[2][0], w1 = s_wcnt[2][1], w2 = s_wcnt[2][2], w3 = s_wcnt[2][3];
+        }
+        if (pass) {
+            const int before = (wave > 0 ? w0 : 0) + (wave > 1 ? w1 : 0) + (wave > 2 ? w2 : 0);
+            const int at = nstage + before + __popcll(bal & ((1ull << lane) - 1ull));      // < 256 by the test above
+            s_sk[at] = key;
+            s_sp[at] = (uint32_t)n;
+        }
+        nstage += w0 + w1 + w2 + w3;
+    }
+    __syncthreads();
+    if (nstage > 0) flush();
+    if (tid < k) {
+        const bool ok = top[0].pos != 0xffffffffu;
+        out_idx[q * k + tid] = ok ? (int32_t)(uint32_t)top[0].key : -1;
+        out_sim[q * k + tid] = ok ? row[top[0].pos] : -INFINITY;
+    }
+}
+
+// One 256-thread workgroup per query, one candidate per thread: T <= 256 is exactly one item per thread of the sorting network
+// above, so the sort is the 256-key case of the code sprc_topk_wide runs (a single wave would hold four items per lane and
+// need a second network for them).  Key = (dist_bits(prob) << 32) | stage-1 position: integer comparisons only, ties keep the
+// stage-1 order.  Padding candidates (id < 0) get the largest distance word and a low word above every position, so they
+// follow every real candidate, a NaN one included, whatever their prob.  The sorted ids then sit in LDS and every thread
+// compares its id with the up to 16 listed ones of the query.
+constexpr int RERANK_L = 16;
+__global__ __launch_bounds__(256) void rerank_order_kernel(const int32_t* __restrict__ cand, const float* __restrict__ prob, int T,
+                                                           const int32_t* __restrict__ listed, const int32_t* __restrict__ listed_rank,
+                                                           int L, int32_t* __restrict__ out_idx, int32_t* __restrict__ out_rank) {
+    __shared__ uint64_t s_xk[256];
+    __shared__ uint32_t s_xp[256];
+    __shared__ int32_t s_listed[RERANK_L];
+    __shared__ int32_t s_rank[RERANK_L];
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    Item it[1];
+    it[0].key = ~0ull;
+    it[0].pos = 0xffffffffu;
+    int32_t id = -1;
+    if (tid < T) {
+        id = cand[q * T + tid];
+        const uint32_t hi = id >= 0 ? dist_bits(prob[q * T + tid]) : 0xffffffffu;
+        it[0].key = ((uint64_t)hi << 32) | (uint32_t)(id >= 0 ? tid : (0x80000000u | tid));
+        it[0].pos = (uint32_t)(id >= 0 ? id : -1);          // the candidate's id travels with the key
+    }
+    if (tid < L) {
+        const int32_t g = listed[q * L + tid];
+        s_listed[tid] = g;
+        s_rank[tid] = g >= 0 ? listed_rank[q * L + tid] : -1;
+    }
+    block_bitonic_sort<1>(it, tid, s_xk, s_xp);             // (has barriers: s_listed / s_rank are visible after it)
+    const int32_t mine = tid < T ? (int32_t)it[0].pos : -1;
+    if (tid < T) out_idx[q * T + tid] = mine;
+    if (mine >= 0)
+        for (int l = 0; l < L; ++l)
+            if (s_listed[l] == mine) s_rank[l] = tid;
+    __syncthreads();
+    if (tid < L) out_rank[q * L + tid] = s_rank[tid];
 }
 
 constexpr int RANK_L = 16;
@@ -277,5 +449,28 @@ extern "C" int sprc_ap_at_k(const float* sim, int64_t ld, const int32_t* gt, int
     else
         hipLaunchKernelGGL(ap_at_k_kernel<32>, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gt, N, G, kk, nk, ap, rank);
     SPRC_CHECK_LAUNCH("sprc_ap_at_k");
+    return SPRC_OK;
+}
+
+extern "C" int sprc_topk_wide(const float* sim, int64_t ld, const int32_t* gidx, int32_t idx_base, const int32_t* skip, int32_t nq,
+                              int32_t N, int32_t k, float* out_sim, int32_t* out_idx, sprc_stream s) {
+    SPRC_REQUIRE(sim && out_sim && out_idx, "sprc_topk_wide: null pointer");
+    SPRC_REQUIRE(nq > 0 && N >= 1 && ld >= N, "sprc_topk_wide: bad shape nq=%d N=%d ld=%lld", nq, N, (long long)ld);
+    SPRC_REQUIRE(k >= 1 && k <= 256, "sprc_topk_wide: k=%d must be in [1,256]", k);
+    ProfScope prof(SPRC_K_RANK, (hipStream_t)s, 0.0, (double)nq * N * (gidx ? 8.0 : 4.0) + (double)nq * k * 8.0);
+    hipLaunchKernelGGL(topk_wide_kernel, dim3(nq), dim3(256), 0, (hipStream_t)s, sim, ld, gidx, idx_base, skip, N, k, out_sim, out_idx);
+    SPRC_CHECK_LAUNCH("sprc_topk_wide");
+    return SPRC_OK;
+}
+
+extern "C" int sprc_rerank_order(const int32_t* cand, const float* prob, int32_t nq, int32_t T, const int32_t* listed,
+                                 const int32_t* listed_rank, int32_t L, int32_t* out_idx, int32_t* out_rank, sprc_stream s) {
+    SPRC_REQUIRE(cand && prob && out_idx, "sprc_rerank_order: null pointer");
+    SPRC_REQUIRE(nq > 0 && T >= 1 && T <= 256, "sprc_rerank_order: bad shape nq=%d T=%d (T must be in [1,256])", nq, T);
+    SPRC_REQUIRE(L >= 0 && L <= RERANK_L, "sprc_rerank_order: L=%d must be in [0,%d]", L, RERANK_L);
+    SPRC_REQUIRE(L == 0 || (listed && listed_rank && out_rank), "sprc_rerank_order: L=%d needs listed, listed_rank and out_rank", L);
+    ProfScope prof(SPRC_K_RANK, (hipStream_t)s, 0.0, (double)nq * T * 12.0 + (double)nq * L * 12.0);
+    hipLaunchKernelGGL(rerank_order_kernel, dim3(nq), dim3(256), 0, (hipStream_t)s, cand, prob, T, listed, listed_rank, L, out_idx, out_rank);
+    SPRC_CHECK_LAUNCH("sprc_rerank_order");
     return SPRC_OK;
 }

@@ -210,6 +210,25 @@ def topk(sim: torch.Tensor, k: int, gidx: Optional[torch.Tensor] = None, idx_bas
     return vals, idx
 
 
+def topk_wide(sim: torch.Tensor, k: int, gidx: Optional[torch.Tensor] = None, idx_base: int = 0,
+              skip: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`topk` for 1 <= k <= 256 (sprc_topk_wide).  skip [nq] (optional): the column position of every row that is left out
+    of the order, negative for none."""
+    lib = L.load()
+    assert sim.dtype == torch.float32 and sim.stride(-1) == 1
+    nq, N = sim.shape
+    vals = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=sim.device)
+    idx = torch.empty((nq, max(k, 0)), dtype=torch.int32, device=sim.device)
+    if gidx is not None:
+        assert gidx.dtype == torch.int32 and gidx.is_contiguous() and gidx.shape == sim.shape
+    if skip is not None:
+        skip = skip.to(device=sim.device, dtype=torch.int32).contiguous()
+        assert skip.shape == (nq,)
+    L.check(lib.sprc_topk_wide(sim.data_ptr(), sim.stride(0), _ptr(gidx), idx_base, _ptr(skip), nq, N, k, vals.data_ptr(),
+                               idx.data_ptr(), _stream()), "sprc_topk_wide")
+    return vals, idx
+
+
 def rank_of(sim: torch.Tensor, listed: torch.Tensor) -> torch.Tensor:
     """Position of listed[q,l] in the stable order of row q (int32; -1 where listed < 0)."""
     lib = L.load()
@@ -220,6 +239,31 @@ def rank_of(sim: torch.Tensor, listed: torch.Tensor) -> torch.Tensor:
     L.check(lib.sprc_rank_of(sim.data_ptr(), sim.stride(0), listed.data_ptr(), nq, N, listed.shape[1], out.data_ptr(),
                              _stream()), "sprc_rank_of")
     return out
+
+
+def rerank_order(cand: torch.Tensor, prob: torch.Tensor, listed: Optional[torch.Tensor] = None,
+                 listed_rank: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Stage-2 re-ordering (sprc_rerank_order): cand [nq,T] gallery indices in stage-1 order (< 0: padding), prob [nq,T] P(match)
+    -> (cand re-ordered by the stable argsort of fl32(1 - prob), int32 [nq,T]; the place of every listed item, int32 [nq,L]:
+    its new position when it is a candidate of its row, listed_rank otherwise, -1 where listed < 0)."""
+    lib = L.load()
+    dev = prob.device
+    cand = cand.to(device=dev, dtype=torch.int32).contiguous()
+    prob = prob.to(dtype=torch.float32).contiguous()
+    assert cand.dim() == 2 and cand.shape == prob.shape
+    nq, T = cand.shape
+    if listed is None:
+        listed = torch.empty((nq, 0), dtype=torch.int32, device=dev)
+        listed_rank = listed
+    listed = listed.to(device=dev, dtype=torch.int32).contiguous()
+    listed_rank = listed_rank.to(device=dev, dtype=torch.int32).contiguous()
+    assert listed.dim() == 2 and listed.shape[0] == nq and listed_rank.shape == listed.shape
+    out_idx, out_rank = torch.empty_like(cand), torch.empty_like(listed)
+    nl = listed.shape[1]
+    L.check(lib.sprc_rerank_order(cand.data_ptr(), prob.data_ptr(), nq, T, listed.data_ptr() if nl else None,
+                                  listed_rank.data_ptr() if nl else None, nl, out_idx.data_ptr(), out_rank.data_ptr() if nl else None,
+                                  _stream()), "sprc_rerank_order")
+    return out_idx, out_rank
 
 
 def ap_at_k(sim: torch.Tensor, gt: torch.Tensor, ks: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -7,7 +7,7 @@ end have no counterpart there: the reference ships the dataset class (src/data_u
 What differs is HOW the metrics are computed: the reference sorts every row of `1 - sim` with
 torch.argsort and then runs O(nq*N) numpy string comparisons (validate_blip.py:253-271).  Here the
 names are mapped to gallery indices once and the ranks come from the HIP ranking kernels
-(sprc_rank_of / sprc_topk): integer-exact, under the stable tie rule (fl32(1-sim), index), with no
+(sprc_rank_of / sprc_topk / sprc_topk_wide / sprc_rerank_order): integer-exact, under the stable tie rule (fl32(1-sim), index), with no
 full sort and no nq x N host traffic.
 """
 from __future__ import annotations
@@ -459,6 +459,27 @@ def cirr_test_dicts_from_sim(sim: torch.Tensor, ref_idx, group_idx, pairs_id, in
     return top, sub
 
 
+def make_rerank_fn(blip_model, index_names: Sequence[str], name_to_feat, reference_names: Sequence[str], ref_idx: Sequence[int],
+                   captions: Sequence[str]):
+    """-> rerank_fn(query_rows[list], cand[len, T] int64 tensor, host or device) -> P(match)[len, T]: the stage-2 scorer of the
+    test-submission and the two validation paths.  Candidates and reference images are RAW embeddings (name_to_feat).
+    A model with `rerank_pairs` scores pairs named by index over ONE `encode_kv` of the gallery (the reference recomputes the
+    K|V projections inside every (query, candidate) pair); any other model of the reference's protocol is called through
+    `inference_rerank` (cirr_test_submission.py:96-102, validate_blip_rerank.py:58-64,207-213)."""
+    if hasattr(blip_model, "rerank_pairs"):
+        kv = blip_model.engine().encode_kv(torch.stack([name_to_feat[n] for n in index_names]).float())
+
+        def rerank_fn(rows, cand):
+            r = torch.tensor([ref_idx[q] for q in rows])
+            return blip_model.rerank_pairs(kv, r, kv, cand, [captions[q] for q in rows])
+    else:
+        def rerank_fn(rows, cand):
+            refs = _stack_refs(name_to_feat, [reference_names[q] for q in rows]).to(blip_model.device)
+            tg = torch.stack([name_to_feat[index_names[i]] for i in cand.reshape(-1).tolist()]).to(blip_model.device)
+            return blip_model.inference_rerank(refs, tg, [captions[q] for q in rows]).view(len(rows), -1)
+    return rerank_fn
+
+
 def generate_cirr_test_dicts(relative_test_dataset, blip_model, index_features, index_names: List[str], txt_processors,
                              rerank=False):
     """-> (pairid -> top-50 names, pairid -> top-3 subset names)   (cirr_test_submission.py:61-132)"""
@@ -471,19 +492,118 @@ def generate_cirr_test_dicts(relative_test_dataset, blip_model, index_features, 
     rerank_fn = None
     if rerank:                              # cirr_test_submission.py:88-112
         print("reranking now")
-        if hasattr(blip_model, "rerank_pairs"):
-            # K|V projections once per gallery image (the reference recomputes them inside every (query, candidate) pair)
-            kv = blip_model.engine().encode_kv(torch.stack([name_to_feat[n] for n in index_names]).float())
-
-            def rerank_fn(rows, cand):
-                r = torch.tensor([ref[q] for q in rows])
-                return blip_model.rerank_pairs(kv, r, kv, cand, [captions[q] for q in rows])
-        else:                               # any model that follows the reference protocol
-            def rerank_fn(rows, cand):
-                refs = _stack_refs(name_to_feat, [reference_names[q] for q in rows]).to(blip_model.device)
-                tg = torch.stack([name_to_feat[index_names[int(i)]] for i in cand.reshape(-1)]).to(blip_model.device)
-                return blip_model.inference_rerank(refs, tg, [captions[q] for q in rows]).view(len(rows), -1)
+        rerank_fn = make_rerank_fn(blip_model, index_names, name_to_feat, reference_names, ref, captions)
     return cirr_test_dicts_from_sim(sim, ref, grp, pairs_id, index_names, rerank_fn=rerank_fn)
+
+
+# ---- two-stage validation: Recall@K after the stage-2 rerank (validate_blip_rerank.py) -------------------------------
+# The project's ranking contract applied to the reference's rerank validation.  The stage-1 order of a row is the stable order
+# by (fl32(1 - sim), index).  CIRR (:184-248) drops the reference image from it, FashionIQ (:42-83) keeps it.  The first
+# T = min(top, entries) places are re-ordered by the stage-2 probabilities under the key (fl32(1 - P), stage-1 position)
+# (sprc_rerank_order; the rule of the test-submission branch above); entries beyond T keep their places.  The reference
+# hard-codes top = 200 / 40 and breaks on a smaller gallery (:215 `reshape(-1, top)`); here T clamps.
+# Two quirks of the reference are NOT reproduced:
+#   * :195 overwrites the order it has just computed with `np.load('sorted_index_names.npy')`, a leftover file read;
+#   * :211 takes the CIRR candidates' features from index_features[0] (the pooled gallery features) where its FashionIQ path
+#     (:62) and cirr_test_submission.py take the raw embeddings.  Candidates here are raw embeddings (K|V via encode_kv), as in
+#     generate_cirr_test_dicts.
+# Device flow: sprc_rank_of (stage-1 ranks of target / reference / members), elementwise ops for the reference-removed
+# ranks, sprc_topk_wide(skip = reference) for the candidates, rerank_fn on blocks of queries, sprc_rerank_order, ONE small
+# copy of ranks to the host.  Nothing is done per query on the host.  The reference's `step` (15 / 40 queries per
+# inference_rerank call) is a batching detail without effect on the result.
+CIRR_RERANK_TOP, FIQ_RERANK_TOP = 200, 40          # validate_blip_rerank.py:200, :51
+RERANK_MAX_TOP = 256                               # sprc_topk_wide / sprc_rerank_order
+RERANK_PAIRS_PER_CALL = 8192                       # (query, candidate) pairs handed to one rerank_fn call; engine.itm chunks them further
+
+
+def _rerank_probs(rerank_fn, cand: torch.Tensor) -> torch.Tensor:
+    """P(match) [nq,T] fp32 on cand's device: rerank_fn over blocks of queries."""
+    nq, T = cand.shape
+    block = max(1, RERANK_PAIRS_PER_CALL // T)
+    prob = torch.empty((nq, T), dtype=torch.float32, device=cand.device)
+    cand64 = cand.to(torch.int64)
+    for s in range(0, nq, block):
+        rows = list(range(s, min(s + block, nq)))
+        prob[s:s + len(rows)] = rerank_fn(rows, cand64[s:s + len(rows)]).detach().reshape(len(rows), T).to(device=cand.device, dtype=torch.float32)
+    return prob
+
+
+def _check_top(top: int, entries: int) -> int:
+    T = min(int(top), entries)
+    if not 1 <= T <= RERANK_MAX_TOP:
+        raise ValueError(f"rerank top={top} over {entries} entries: between 1 and {RERANK_MAX_TOP} candidates are re-ordered")
+    return T
+
+
+def cirr_rerank_metrics_from_sim(sim: torch.Tensor, ref_idx, tgt_idx, group_idx, rerank_fn, top: int = CIRR_RERANK_TOP) -> Tuple[float, ...]:
+    """-> (group_recall@1, @2, @3, recall@1, @5, @10, @50) after the stage-2 rerank   (validate_blip_rerank.py:184-248)
+    Stable order by (fl32(1 - sim), index); the reference image is dropped (:189-193); the first T = min(top, N - 1) entries
+    are re-ordered by rerank_fn's probabilities (:197-220; key (fl32(1 - P), stage-1 position)), the others keep their places.
+    Recall@K from the target's position (:225,238-241); subset recall from the number of group members (not the reference,
+    not missing from the gallery) placed before the target (:229-235,242-244), counted as in `cirr_metrics_from_sim`.
+    rerank_fn(query_rows[list], cand[len, T] int64 tensor) -> P(match)[len, T]; cand and the result may live on the device."""
+    ref_np, tgt_np, grp_np = (np.asarray(a, dtype=np.int64) for a in (ref_idx, tgt_idx, group_idx))
+    assert (tgt_np != ref_np).all() and (tgt_np >= 0).all(), "every query needs its target in the gallery, distinct from the reference"
+    assert ((grp_np == tgt_np[:, None]).sum(1) == 1).all(), "target must appear exactly once among the group members"     # :235
+    sim = sim.contiguous()
+    dev = sim.device
+    T = _check_top(top, sim.shape[1] - 1)
+    ref = torch.from_numpy(ref_np).to(dev)
+    listed = torch.from_numpy(np.concatenate([tgt_np[:, None], grp_np], axis=1)).to(dev)          # [nq, 1 + 6]
+    ranks = E.rank_of(sim, torch.cat([ref[:, None], listed], dim=1))
+    r_ref, r = ranks[:, :1], ranks[:, 1:]
+    r = r - (r_ref < r).to(r.dtype)                                       # :189-193: places in the reference-less order
+    listed = torch.where((listed >= 0) & (listed != ref[:, None]), listed, torch.full_like(listed, -1))
+    _, cand = E.topk_wide(sim, T, skip=ref)
+    _, place = E.rerank_order(cand, _rerank_probs(rerank_fn, cand), listed, r)
+    place = place.cpu().numpy().astype(np.int64)                          # the one copy to the host: [nq, 1 + 6] places
+    r_t, r_g = place[:, 0], place[:, 1:]
+    pos_in_group = ((r_g < r_t[:, None]) & (r_g >= 0)).sum(1)
+    return (_pct(pos_in_group < 1), _pct(pos_in_group < 2), _pct(pos_in_group < 3),
+            _pct(r_t < 1), _pct(r_t < 5), _pct(r_t < 10), _pct(r_t < 50))
+
+
+def fiq_rerank_metrics_from_sim(sim: torch.Tensor, tgt_idx, rerank_fn, top: int = FIQ_RERANK_TOP) -> Tuple[float, float]:
+    """-> (recall@10, recall@50) after the stage-2 rerank   (validate_blip_rerank.py:42-83)
+    As `cirr_rerank_metrics_from_sim` without the removal of the reference image: T = min(top, N)."""
+    tgt_np = np.asarray(tgt_idx, dtype=np.int64)
+    assert (tgt_np >= 0).all(), "every query needs its target in the gallery"                     # :77
+    sim = sim.contiguous()
+    T = _check_top(top, sim.shape[1])
+    listed = torch.from_numpy(tgt_np[:, None]).to(sim.device)
+    _, cand = E.topk_wide(sim, T)
+    _, place = E.rerank_order(cand, _rerank_probs(rerank_fn, cand), listed, E.rank_of(sim, listed))
+    r = place.cpu().numpy()[:, 0]
+    return _pct(r < 10), _pct(r < 50)
+
+
+def compute_cirr_val_metrics_rerank(relative_val_dataset, blip_model, index_features, index_names: List[str], txt_processors,
+                                    top: int = CIRR_RERANK_TOP):
+    """-> (group_recall@1, @2, @3, recall@1, @5, @10, @50) of the two-stage pipeline   (validate_blip_rerank.py:165-248;
+    see `cirr_rerank_metrics_from_sim` and the section comment above for the rule and the reference's two quirks)."""
+    sim, reference_names, target_names, group_members, captions = generate_cirr_val_predictions(
+        blip_model, relative_val_dataset, index_names, index_features, txt_processors)
+    print("Compute CIRR validation metrics")
+    n2i = {n: i for i, n in enumerate(index_names)}
+    ref = [n2i[n] for n in reference_names]
+    tgt = [n2i[n] for n in target_names]
+    grp = [[n2i.get(n, -1) for n in g] for g in group_members]
+    print("reranking now")
+    rerank_fn = make_rerank_fn(blip_model, index_names, dict(zip(index_names, index_features[1])), reference_names, ref, captions)
+    return cirr_rerank_metrics_from_sim(sim, ref, tgt, grp, rerank_fn, top=top)
+
+
+def compute_fiq_val_metrics_rerank(relative_val_dataset, blip_model, index_features, index_names: List[str], txt_processors,
+                                   save_memory: bool = False, top: int = FIQ_RERANK_TOP) -> Tuple[float, float]:
+    """-> (recall@10, recall@50) of the two-stage pipeline; the reference image is NOT removed   (validate_blip_rerank.py:23-83)"""
+    sim, target_names, reference_names, captions = generate_fiq_val_predictions(blip_model, relative_val_dataset, index_names,
+                                                                                index_features, txt_processors, save_memory)
+    print(f"Compute FashionIQ {getattr(relative_val_dataset, 'dress_types', '')} validation metrics")
+    n2i = {n: i for i, n in enumerate(index_names)}
+    print("reranking now")
+    rerank_fn = make_rerank_fn(blip_model, index_names, dict(zip(index_names, index_features[-1])), reference_names,
+                               [n2i[n] for n in reference_names], captions)
+    return fiq_rerank_metrics_from_sim(sim, [n2i[n] for n in target_names], rerank_fn, top=top)
 
 
 # ---- CIRCO: validation metrics (mAP@K over several ground truths) and test submission ---------------------------------

@@ -3,7 +3,8 @@
 4181 triplets, the reference's directory / JSON layout), a full-depth ViT-g checkpoint file with the reference's key layout, then
 `python -m sprc_amd.blip_validate --dataset CIRR` as the reference's script is run (src/blip_validate.py:103-155): image
 decoding, the transform, gallery encoding, query fusion, ranking, metrics.  Prints the wall-clock of each variant.
-Usage (GPU box): tools/c2_e2e.py [n_images n_queries]      -- writes under $TMPDIR/sprc_c2"""
+Usage (GPU box): tools/c2_e2e.py [n_images n_queries] [--rerank]      -- writes under $TMPDIR/sprc_c2
+--rerank: time `blip_validate --rerank true` alone (the two-stage validation: 200 stage-2 pairs per query)."""
 import json
 import os
 import sys
@@ -19,8 +20,9 @@ sys.path.insert(0, str(ROOT))
 from sprc_amd import synth  # noqa: E402
 from sprc_amd.config import get_config  # noqa: E402
 
-N_IMG = int(sys.argv[1]) if len(sys.argv) > 1 else 2297
-NQ = int(sys.argv[2]) if len(sys.argv) > 2 else 4181
+_SIZES = [a for a in sys.argv[1:] if not a.startswith("--")]
+N_IMG = int(_SIZES[0]) if len(_SIZES) > 0 else 2297
+NQ = int(_SIZES[1]) if len(_SIZES) > 1 else 4181
 def synth_image(w: int, h: int, seed: int) -> np.ndarray:
     """uint8 RGB [h, w, 3]: smooth gradients + blocks + noise (enough structure for the bicubic transform to matter)"""
     rng = np.random.default_rng(seed)
@@ -118,6 +120,17 @@ def main():
         breakdown(root)
     base = ["--dataset", "CIRR", "--model-path", str(root / "ckpt.pt")]
     out = {}
+    if "--rerank" in sys.argv[1:]:               # (the checkpoint is align_prompt's: it carries itm_head.*, as the submission's rerank needs)
+        # the two-stage validation alone (validate_blip_rerank.py): stage 1 as above + the first 200 of every query re-scored
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        m = bv.main(base + ["--gpu-preprocess", "--rerank", "true"])
+        torch.cuda.synchronize()
+        out["two-stage validation (GPU transform, top 200)"] = time.perf_counter() - t
+        print(f"[c2_e2e] two-stage validation: {time.perf_counter() - t:.1f} s for {NQ} x {min(200, N_IMG - 1)} stage-2 pairs   "
+              f"R@1 {m['recall_at1']:.2f} R@10 {m['recall_at10']:.2f} Rs@1 {m['group_recall_at1']:.2f}", flush=True)
+        print(json.dumps({"n_images": N_IMG, "n_queries": NQ, "seconds": out}))
+        return
     for tag, extra in (("PIL transform in loader workers", []), ("GPU transform", ["--gpu-preprocess"]),
                        ("GPU transform, gallery from the feature store", ["--gpu-preprocess", "--index-cache", str(root / "index")]),
                        ("GPU transform, gallery from the feature store (second run)", ["--gpu-preprocess", "--index-cache", str(root / "index")])):
