@@ -528,6 +528,44 @@ int sprc_l2norm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, 
 int sprc_align_mse_bwd(const float* h, int64_t sample_stride, int32_t Lq, int32_t D, const float* prompt, int32_t B, float grad, float* dh,
                        int64_t d_stride, sprc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Optimiser step: the parameter update of the reference's fine-tuning loops in one launch.  Replaces
+ * `optim.AdamW(... betas (0.9, 0.98), eps 1e-7, weight_decay 0.05)` of blip_fine_tune_2.py:257-259 (CIRR) and :90-93 (FashionIQ)
+ * together with the unscale, the host read of found_inf and the step that `scaler.step(optimizer)` performs at :302 (:136) -- in torch
+ * about a dozen foreach passes over the 337 trainable tensors and a host sync.  ONE pass over p, m and v; the inf CHECK is not
+ * replaced: found_inf is an input, and behind the stock GradScaler torch still makes one foreach pass over the gradients to produce it.
+ *
+ * Arithmetic, per element, fp32, in exactly this order with no contraction (torch's _single_tensor_adam, decoupled weight decay):
+ *     g' = g * inv_scale                  inv_scale = float(1 / grad_scale)
+ *     p  = p * c_wd                       c_wd = float(1 - lr * weight_decay)
+ *     m  = m + w1 * (g' - m)              w1   = float(1 - beta1)                 (torch lerp, weight < 0.5)
+ *     v  = v * beta2 + (w2 * g') * g'     w2   = float(1 - beta2)
+ *     d  = sqrt(v) / bc2s + eps           bc2s = float(sqrt(1 - beta2^t))
+ *     p  = p + nss * (m / d)              nss  = float(-(lr / (1 - beta1^t)))
+ * t = the number of applied steps AFTER this one.  The scalars are formed in fp64 from the doubles below and rounded once, as
+ * torch forms them in Python floats -- on the device, because t lives there: a step that found_inf skips must not advance it and
+ * the host is never told.  A one-wave prologue kernel reads found_inf / grad_scale / step, advances step and leaves the scalars
+ * and a skip flag in `scratch`; the update kernel reads them and returns at once when the step is skipped.
+ * ---------------------------------------------------------------------------------------- */
+
+#define SPRC_OPT_CHUNK 4096                   /* elements of one tensor that one workgroup updates at a time */
+
+typedef struct { float* p; const float* g; float* m; float* v; int64_t n; } sprc_opt_tensor;   /* one trainable tensor: fp32, contiguous */
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;   /* THIS step's values (OneCycleLR moves lr and beta1 every step); doubles, as the
+                                                     param group holds them: float(1 - beta) must not start from a rounded beta */
+    const float* grad_scale;   /* device fp32[1] or NULL (= 1): the gradient used is g * float(1 / grad_scale[0]); g is NOT written */
+    const float* found_inf;    /* device fp32[1] or NULL (= 0): non-zero -> p, m, v and step are left untouched, bit for bit */
+    float* step;               /* device fp32[1]: number of APPLIED steps; += 1 unless skipped */
+    void* scratch;             /* device, >= 64 bytes, 8-byte aligned: this call's scalars; must not be shared by calls in flight */
+} sprc_adamw_args;
+
+/* One call updates every tensor of a parameter group.  tensors: DEVICE array [n_tensors] (n >= 1 each); chunk_first: DEVICE int32
+ * [n_tensors + 1], prefix sums of ceil(n / SPRC_OPT_CHUNK) starting at 0; n_chunks: its last entry.  The caller builds and uploads
+ * both (on stream s, or earlier).  16-byte accesses wherever p, g, m and v of a tensor are all 16-byte aligned, 4-byte ones otherwise. */
+int sprc_adamw_step(const sprc_opt_tensor* tensors, int32_t n_tensors, const int32_t* chunk_first, int32_t n_chunks,
+                    const sprc_adamw_args* a, sprc_stream s);
+
 #ifdef __cplusplus
 }
 #endif

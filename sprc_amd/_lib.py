@@ -110,6 +110,18 @@ class QformerModel(C.Structure):
                 ("layers", C.POINTER(QfLayer)), ("x3", i32), ("x3_image", i32), ("x3_fuse", i32)]
 
 
+OPT_CHUNK = 4096                                      # SPRC_OPT_CHUNK
+
+
+class OptTensor(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64)]
+
+
+class AdamWArgs(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("grad_scale", vp), ("found_inf", vp), ("step", vp), ("scratch", vp)]
+
+
 # name -> (restype, argtypes); must list every symbol include/sprc.h declares
 SIGNATURES = {
     "sprc_version": (i32, []),
@@ -172,6 +184,7 @@ SIGNATURES = {
     "sprc_align_mse_bwd": (i32, [vp, i64, i32, i32, vp, i32, f32, vp, i64, vp]),
     "sprc_preprocess_workspace_bytes": (sz, [i32, i32, f32, i32]),
     "sprc_preprocess_targetpad": (i32, [vp, i32, i32, i64, f32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, sz, vp]),
+    "sprc_adamw_step": (i32, [vp, i32, vp, i32, C.POINTER(AdamWArgs), vp]),
 }
 
 _lib = None

@@ -6,7 +6,9 @@ loops apply to every caption (validate_blip.py:389, :185; cirr_test_submission.p
 """
 from __future__ import annotations
 
+import random
 import re
+from typing import List
 
 
 class BlipCaptionProcessor:
@@ -35,3 +37,22 @@ class BlipCaptionProcessor:
 def fiq_compose_caption(c1: str, c2: str) -> str:
     """FashionIQ's two relative captions -> one (validate_blip.py:180-184, R10)."""
     return f"{c1.strip('.?, ').capitalize()} and {c2.strip('.?, ')}"
+
+
+def generate_randomized_fiq_caption(flattened_captions: List[str]) -> List[str]:
+    """The FashionIQ TRAINING captions (utils.py:117-138): of every caption pair (2i, 2i + 1) one of "A and b", "B and a", "A", "B",
+    chosen by one draw of Python's `random` per pair -- `random.seed` reproduces the reference's choices.  The reference compares
+    strictly on both sides, so a draw of exactly 0.25, 0.5 or 0.75 falls through to the last form; that is kept."""
+    out = []
+    for i in range(0, len(flattened_captions), 2):
+        a, b = flattened_captions[i].strip(".?, "), flattened_captions[i + 1].strip(".?, ")
+        r = random.random()
+        if r < 0.25:
+            out.append(f"{a.capitalize()} and {b}")
+        elif 0.25 < r < 0.5:
+            out.append(f"{b.capitalize()} and {a}")
+        elif 0.5 < r < 0.75:
+            out.append(a.capitalize())
+        else:
+            out.append(b.capitalize())
+    return out
