@@ -511,7 +511,11 @@ typedef struct {
 int sprc_dropout_f32(const float* x, const float* resid, float* y, size_t n, uint64_t seed, uint32_t site, float p, sprc_stream s);
 int sprc_attention_bwd(const sprc_attention_bwd_args* a, sprc_stream s);
 /* The rows sprc_qformer_embed normalises, WITHOUT the LayerNorm (pre [B, Lq+Lt, hidden]), and the scatter of their gradient:
- * dquery[b * dq_bstride + row] += (dq_bstride 0: summed over the batch), dword[id] +=, dpos[position] += (atomic adds). */
+ * dquery[b * dq_bstride + row] += (dq_bstride 0: summed over the batch), dword[id] +=, dpos[position] += (atomic adds).
+ * Both refuse, before any launch: B <= 0, Lq < 0, Lt < 0, Lq + Lt == 0, hidden <= 0 (the forward also hidden % 4 != 0), and
+ * no_img != 0 with Lt < 1 -- the text-only layout [CLS | query rows | text[1:]] reads input_ids[b * Lt] for row 0 of every sample,
+ * so it needs a first token.  Lt == 0 (image mode) takes NULL text pointers.  The backward makes the forward's shape checks because
+ * its scatter walks the same rows; dquery may be NULL (no query gradient wanted), dword / dpos only when Lt == 0. */
 int sprc_qformer_embed_rows(const sprc_qformer_embed_args* a, float* pre, sprc_stream s);
 int sprc_qformer_embed_bwd(const sprc_qformer_embed_args* a, const float* dpre, float* dquery, int64_t dq_bstride, float* dword, float* dpos,
                            sprc_stream s);

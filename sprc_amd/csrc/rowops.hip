@@ -405,6 +405,9 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void itm_head_kernel(const flo
 // ---- training-forward losses (align_prompt.py:157-193) -------------------------------------------------------------------
 // loss = mean_b( logsumexp_n(sim[b,n] / temp) - sim[b,b] / temp ): F.cross_entropy(sim / temp, arange(B)).  One workgroup.
 __global__ __launch_bounds__(256) void contrastive_ce_kernel(const float* __restrict__ sim, int64_t ld, int B, float inv_temp, float* loss) {
+    // every sim * inv_temp below rounds on its own: contracted into the subtractions, the target's logit entered the last line as an EXACT
+    // product against the ROUNDED one inside mx, and a batch of one gave a loss of 1e-8 instead of 0
+#pragma clang fp contract(off)
     __shared__ float part[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float acc = 0.f;

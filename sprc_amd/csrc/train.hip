@@ -541,7 +541,9 @@ extern "C" int sprc_attention_bwd(const sprc_attention_bwd_args* a, sprc_stream 
 
 extern "C" int sprc_qformer_embed_rows(const sprc_qformer_embed_args* a, float* pre, sprc_stream s) {
     SPRC_REQUIRE(a && pre && (a->query_embeds || a->Lq == 0), "sprc_qformer_embed_rows: null pointer");
-    SPRC_REQUIRE(a->B > 0 && a->Lq >= 0 && a->Lt >= 0 && a->Lq + a->Lt > 0 && a->hidden % 4 == 0, "sprc_qformer_embed_rows: bad shape");
+    SPRC_REQUIRE(a->B > 0 && a->Lq >= 0 && a->Lt >= 0 && a->Lq + a->Lt > 0 && a->hidden > 0 && a->hidden % 4 == 0, "sprc_qformer_embed_rows: bad shape");
+    // text-only layout [CLS | prompt rows | text[1:]]: row 0 of every sample reads input_ids[b * Lt], so there must be a token to read
+    SPRC_REQUIRE(!a->no_img || a->Lt >= 1, "sprc_qformer_embed_rows: no_img needs Lt >= 1 (row 0 is the first text token)");
     SPRC_REQUIRE(a->Lt == 0 || (a->input_ids && a->word_emb && a->pos_emb), "sprc_qformer_embed_rows: text tables missing");
     hipLaunchKernelGGL(embed_rows_kernel, dim3(grid1d((int64_t)a->B * (a->Lq + a->Lt) * (a->hidden / 4))), dim3(256), 0, (hipStream_t)s, *a, pre);
     SPRC_CHECK_LAUNCH("sprc_qformer_embed_rows");
@@ -551,6 +553,9 @@ extern "C" int sprc_qformer_embed_rows(const sprc_qformer_embed_args* a, float* 
 extern "C" int sprc_qformer_embed_bwd(const sprc_qformer_embed_args* a, const float* dpre, float* dquery, int64_t dq_bstride, float* dword,
                                       float* dpos, sprc_stream s) {
     SPRC_REQUIRE(a && dpre, "sprc_qformer_embed_bwd: null pointer");
+    // the forward's shape checks (the scatter walks the same rows); dquery == NULL: the caller wants no query gradient
+    SPRC_REQUIRE(a->B > 0 && a->Lq >= 0 && a->Lt >= 0 && a->Lq + a->Lt > 0 && a->hidden > 0, "sprc_qformer_embed_bwd: bad shape");
+    SPRC_REQUIRE(!a->no_img || a->Lt >= 1, "sprc_qformer_embed_bwd: no_img needs Lt >= 1 (row 0 is the first text token)");
     SPRC_REQUIRE(a->Lt == 0 || (a->input_ids && dword && dpos), "sprc_qformer_embed_bwd: text gradients need input_ids, dword, dpos");
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(grid1d((int64_t)a->B * (a->Lq + a->Lt) * a->hidden)), dim3(256), 0, (hipStream_t)s, *a, dpre, dquery,
                        dq_bstride, dword, dpos);

@@ -182,7 +182,6 @@ class _Linear:
         """dW += dy^T x, db += colsum(dy); returns dx (+ acc: the running gradient of x from other paths) or None.
         shared: x is read by several linears of this step (1: cache its transpose, 2: this is its last consumer)."""
         k = self.k
-        assert self.W.shape[0] % 32 == 0 or not need_dx, "dX = dY . W reduces over the N output features: the fp32 GEMM needs N % 32 == 0"
         xt = k.transpose_saved(x, last=shared == 2) if shared else k.transpose(x)
         k.gemm(k.transpose(dy), xt, resid=self.gW, out=self.gW)
         if self.gb is not None:
@@ -190,9 +189,16 @@ class _Linear:
         if not need_dx:
             return None
         if self._Wt is None:
-            self._Wt = k.transpose(self.W, pad=32)           # [K, N]: dX = dY . W reduces over the N output features
-        Wt = self._Wt[:, :self.W.shape[0]] if self._Wt.shape[1] != self.W.shape[0] else self._Wt
-        return k.gemm(dy, Wt, resid=acc, out=acc)
+            self._Wt = k.transpose(self.W, pad=32)           # [K, N padded]: dX = dY . W reduces over the N output features
+        # the GEMM's reduction length is a multiple of its K-tile (32 fp32 / 64 fp16 elements): where N is not, the reduction runs over the
+        # zero-padded columns of W^T and dY gets the same zero columns (a copy: data movement only).  (A [:, :N] slice of W^T was refused
+        # by sprc_gemm for exactly the N that need it; no layer of the model has such an N.)
+        N, Np = self.W.shape[0], self._Wt.shape[1]
+        if Np != N:
+            dyp = k.zeros(dy.shape[0], Np)
+            dyp[:, :N].copy_(dy)
+            dy = dyp
+        return k.gemm(dy, self._Wt, resid=acc, out=acc)
 
 
 # dropout sites (the numbering of oracle/sprc_oracle.py: drop_site): pass * 256 + layer * 8 + kind, embeddings pass * 256 + 255
