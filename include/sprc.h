@@ -245,6 +245,15 @@ int sprc_qformer_mask(const int64_t* attention_mask, float* out, int32_t B, int3
 int sprc_sim_max(const void* fusion, const void* feats, float* sim, int64_t ld_sim,
                  int32_t nq, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
 
+/* The same scores for a FEW queries against a stored gallery (index search): feats [N,32,E] is streamed from HBM once,
+ * global -> VGPR -> MFMA, no LDS (csrc/search.hip).  1 <= nq <= 32, E == 256, dtype SPRC_F16 or SPRC_BF16, N >= 1, ld_sim >= N,
+ * fusion and feats 16-byte aligned; anything else is SPRC_EINVAL before any launch.  Writes sim[q, 0..N) for q < nq and nothing
+ * else; allocates nothing, does not synchronise.  Products of the 16-bit operands, fp32 accumulation in the kernel's own order
+ * over E (not sprc_sim_max's: equal bits only where the fp32 sums are exact), max in fp32.  NaN / Inf operands: no fault, values
+ * unspecified. */
+int sprc_sim_max_stream(const void* fusion, const void* feats, float* sim, int64_t ld_sim,
+                        int32_t nq, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
+
 /* Per row of sim[nq,N] (ld in elements): the k smallest keys (fl32(1 - sim[n]), gidx[n]) ascending,
  * i.e. the first k entries of a STABLE argsort of the fp32 distance (the ranking contract,
  * SURVEY.md section 7).  gidx: optional int32 [nq,N] global indices (NULL -> n + idx_base).

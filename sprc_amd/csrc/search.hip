@@ -1,0 +1,117 @@
+// search.hip -- index search: streaming small-batch scoring (sprc_sim_max_stream).
+//
+// sim[q, n] = max_j <fusion[q,:], feats[n,j,:]> for 1 <= nq <= 32 queries against a gallery that is read from HBM exactly once:
+// 16 KiB per image (16-bit), 2 * 32 * 256 * nq flops per image -- at nq = 1 almost no arithmetic per byte.  sprc_sim_max runs this
+// as a GEMM with M = nq on 256-row tiles and stages both operands through LDS; here the gallery goes global -> VGPR -> MFMA.
+//
+// One image per wave per 16 v_mfma_f32_32x32x16_{f16,bf16}:
+//   A = the image's 32 feature rows: lane (r = l & 31, h = l >> 5) holds feats[n, r, 16 t + 8 h .. + 7] for k-step t -- one 16-B load
+//       per k-step, 16 loads (64 VGPRs) per image;
+//   B = the queries, zero-padded to 32 columns: lane (r, h) holds fusion[q = r, 16 t + 8 h .. + 7]; loaded once, 64 VGPRs for the
+//       whole launch;
+//   D = [feature row j][query q]: q on the lane (col = l & 31), j in the 16 registers x 2 lane halves, so max_j is 15 in-lane
+//       v_max_f32 and one exchange between the halves.
+// A wave holds two images' operands: the loads of images i + 2, i + 3 are issued behind the MFMAs of images i, i + 1 (hipcc
+// interleaves the two chains) and every MFMA waits for its own fragment only (counted vmcnt, 5 .. 31 in the listing; 0 only in the
+// peeled last trip, which fetches nothing).  No LDS, no barrier.  A workgroup (4 waves)
+// takes STREAM_P = 8 consecutive images per loop trip and a contiguous range of trips; the grid is 2 workgroups per CU (256
+// VGPRs each), so a CU has 16 images = 256 KiB in flight.  After a pair of images the lanes of half 0 store the first image's
+// scores and the lanes of half 1 the second's: one store instruction per pair, 8 contiguous bytes per query.
+// Products of 16-bit operands are exact in fp32; the sum runs in the MFMA's order over k (not the GEMM's K-tile order).
+#include "common.hpp"
+
+namespace sprc {
+
+constexpr int STREAM_P = 8;              // images per workgroup per loop trip (sprc_amd/engine.py: STREAM_P)
+constexpr int STREAM_WG_PER_CU = 2;
+constexpr int STREAM_E = 256;
+constexpr int STREAM_IMG_BYTES = 32 * STREAM_E * 2;
+
+template <bool F16>
+__device__ __forceinline__ f32x16 stream_mfma(const u32x4& a, const u32x4& b, f32x16 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// the 16 operand loads of image n (clamped to the last image: a load is never predicated, so the compiler's waits stay counted)
+__device__ __forceinline__ void stream_load(u32x4 (&a)[16], const char* lane_base, int n, int N) {
+    const u32x4* p = reinterpret_cast<const u32x4*>(lane_base + (int64_t)min(n, N - 1) * STREAM_IMG_BYTES);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) a[t] = p[2 * t];
+}
+
+template <bool F16>
+__device__ __forceinline__ f32x16 stream_dot(const u32x4 (&a)[16], const u32x4 (&q)[16]) {
+    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 16; ++t) acc = stream_mfma<F16>(a[t], q[t], acc);
+    return acc;
+}
+
+// max over the 32 feature rows of the lane's query: 16 registers, then the other lane half
+__device__ __forceinline__ float stream_rowmax(const f32x16& acc) {
+    float m = acc[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) m = fmaxf(m, acc[i]);
+    return fmaxf(m, __shfl_xor(m, 32, 64));
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void sim_max_stream_kernel(const char* __restrict__ fusion, const char* __restrict__ feats,
+                                                                float* __restrict__ sim, int64_t ld, int nq, int N, int trips) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    u32x4 q[16];
+    {
+        const u32x4* p = reinterpret_cast<const u32x4*>(fusion + (int64_t)min(r, nq - 1) * (STREAM_E * 2) + h * 16);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const u32x4 v = p[2 * t];
+            q[t] = r < nq ? v : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    const int t0 = (int)((int64_t)blockIdx.x * trips / gridDim.x), t1 = (int)((int64_t)(blockIdx.x + 1) * trips / gridDim.x);
+    if (t0 >= t1) return;
+    const char* lane_base = feats + r * (STREAM_E * 2) + h * 16;
+    float* out = sim + (int64_t)r * ld + h;          // lane (r, h) stores image n + h of its pair
+    int n = t0 * STREAM_P + 2 * wave;                // first image of this wave's pair in the current trip
+    u32x4 a0[16], a1[16];
+    stream_load(a0, lane_base, n, N);
+    stream_load(a1, lane_base, n + 1, N);
+    for (int trip = t0; trip + 1 < t1; ++trip, n += STREAM_P) {
+        const f32x16 c0 = stream_dot<F16>(a0, q);
+        stream_load(a0, lane_base, n + STREAM_P, N);
+        const f32x16 c1 = stream_dot<F16>(a1, q);
+        stream_load(a1, lane_base, n + STREAM_P + 1, N);
+        const float m0 = stream_rowmax(c0), m1 = stream_rowmax(c1);
+        if (r < nq && n + h < N) out[n] = h ? m1 : m0;
+    }
+    const float m0 = stream_rowmax(stream_dot<F16>(a0, q)), m1 = stream_rowmax(stream_dot<F16>(a1, q));
+    if (r < nq && n + h < N) out[n] = h ? m1 : m0;
+}
+
+}  // namespace sprc
+
+using namespace sprc;
+
+extern "C" int sprc_sim_max_stream(const void* fusion, const void* feats, float* sim, int64_t ld_sim, int32_t nq, int32_t N, int32_t E,
+                                   int32_t dtype, sprc_stream s) {
+    SPRC_REQUIRE(fusion && feats && sim, "sprc_sim_max_stream: null pointer");
+    SPRC_REQUIRE(nq >= 1 && nq <= 32, "sprc_sim_max_stream: nq=%d must be in [1,32] (walk more queries in blocks of 32)", nq);
+    SPRC_REQUIRE(E == STREAM_E, "sprc_sim_max_stream: E=%d must be %d", E, STREAM_E);
+    SPRC_REQUIRE(dtype == SPRC_F16 || dtype == SPRC_BF16, "sprc_sim_max_stream: dtype %d must be SPRC_F16 or SPRC_BF16", dtype);
+    SPRC_REQUIRE(N >= 1 && ld_sim >= N, "sprc_sim_max_stream: bad shape N=%d ld_sim=%lld", N, (long long)ld_sim);
+    SPRC_REQUIRE(((uintptr_t)fusion & 15) == 0 && ((uintptr_t)feats & 15) == 0, "sprc_sim_max_stream: fusion and feats must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)s;
+    const int trips = (int)(((int64_t)N + STREAM_P - 1) / STREAM_P);
+    const int grid = min(trips, STREAM_WG_PER_CU * stream_cus(st));
+    ProfScope prof(SPRC_K_RANK, st, 2.0 * nq * (double)N * 32.0 * E, (double)N * STREAM_IMG_BYTES + (double)nq * E * 2.0 + (double)nq * N * 4.0);
+    const char* f = (const char*)fusion;
+    const char* g = (const char*)feats;
+    if (dtype == SPRC_F16)
+        hipLaunchKernelGGL(sim_max_stream_kernel<true>, dim3(grid), dim3(256), 0, st, f, g, sim, ld_sim, nq, N, trips);
+    else
+        hipLaunchKernelGGL(sim_max_stream_kernel<false>, dim3(grid), dim3(256), 0, st, f, g, sim, ld_sim, nq, N, trips);
+    SPRC_CHECK_LAUNCH("sprc_sim_max_stream");
+    return SPRC_OK;
+}

@@ -291,3 +291,32 @@ class CIRCODataset(_Base):
 
     def __len__(self):
         return len(self.annotations) if self.mode == "relative" else len(self.img_ids)
+
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".gif", ".tif", ".tiff")
+
+
+class ImageDirDataset(_Base):
+    """A directory of image files as a gallery (`python -m sprc_amd.search build`): 'classic' items (name, image) like the other
+    datasets of this file, the name being the file's stem.  Files are walked recursively and taken in sorted name order; two
+    files with one stem are an error (names are the join key of a feature store).  No reference counterpart."""
+
+    split, mode = "", "classic"
+
+    def __init__(self, root: Union[str, Path], preprocess: Callable):
+        self.root, self.preprocess = Path(root), preprocess
+        if not self.root.is_dir():
+            raise FileNotFoundError(f"{self.root} is not a directory")
+        paths = sorted((p for p in self.root.rglob("*") if p.is_file() and p.suffix.lower() in IMAGE_SUFFIXES), key=lambda p: (p.stem, str(p)))
+        for a, b in zip(paths, paths[1:]):
+            if a.stem == b.stem:
+                raise ValueError(f"duplicate image name {a.stem!r}: {a} and {b}")
+        self.paths = paths
+        self.names = [p.stem for p in paths]
+
+    def _get(self, index):
+        from PIL import Image
+        return self.names[index], self.preprocess(Image.open(self.paths[index]))
+
+    def __len__(self):
+        return len(self.paths)

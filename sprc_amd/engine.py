@@ -229,6 +229,95 @@ def topk_wide(sim: torch.Tensor, k: int, gidx: Optional[torch.Tensor] = None, id
     return vals, idx
 
 
+STREAM_P = 8                # images one workgroup of sprc_sim_max_stream takes per loop trip (csrc/search.hip: STREAM_P)
+STREAM_WG_PER_CU = 2        # its grid: min(ceil(N / STREAM_P), STREAM_WG_PER_CU * CUs) workgroups, a contiguous range of trips each
+STREAM_MAX_NQ = 32          # queries of one launch (the columns of one MFMA tile)
+
+
+def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sim_max` for few queries against a stored 16-bit gallery (sprc_sim_max_stream: the gallery is streamed from HBM once, no
+    LDS); fusion [nq,256], feats [N,32,256], both fp16 or both bf16.  More than 32 queries are walked in blocks of 32 into one sim."""
+    lib = L.load()
+    nq, E = fusion.shape
+    N, J, E2 = feats.shape
+    assert J == 32 and E2 == E and fusion.dtype == feats.dtype and fusion.is_contiguous() and feats.is_contiguous()
+    dt = _SPRC_DT[fusion.dtype]
+    if out is None:
+        out = torch.empty((nq, N), dtype=torch.float32, device=fusion.device)
+    assert out.dtype == torch.float32 and out.shape == (nq, N) and (N == 1 or out.stride(1) == 1)
+    for q0 in range(0, max(nq, 1), STREAM_MAX_NQ):
+        nb = min(STREAM_MAX_NQ, nq - q0)
+        L.check(lib.sprc_sim_max_stream(fusion[q0:].data_ptr(), feats.data_ptr(), out[q0:].data_ptr(), out.stride(0), nb, N, E, dt,
+                                        _stream()), "sprc_sim_max_stream")
+    return out
+
+
+def search_segments(nq: int, N: int, S: Optional[int] = None) -> Tuple[int, int]:
+    """How `search_topk` cuts a row of N scores for its first level -> (segment length L, number of segments ceil(N / L)): segments
+    [s L, min((s + 1) L, N)), all of length L but possibly the last.  S forces the number asked for (it is clamped to N and L is
+    rounded up, so fewer segments may come out); the rule otherwise depends on (nq, N) only.
+    One row is one workgroup of sprc_topk, which walks it 256 scores per step: a row of N costs N / 256 dependent steps on ONE CU,
+    S segments cost N / (256 S) steps each on S CUs plus S k / 256 steps for the merge of the S k candidates.  With k of the order
+    of 64 the sum is least near S = sqrt(N / 64); rows below 8192 scores (32 steps) stay whole, and nq S is kept near 1024
+    workgroups (four per CU) because more queries already fill the chip."""
+    if N < 1 or nq < 1:
+        raise ValueError(f"search_segments: nq={nq} N={N}")
+    if S is None:
+        S = 1 if N < 8192 else max(1, min(int((N // 64) ** 0.5), 1024 // nq))
+    S = max(1, min(int(S), N))
+    seg = -(-N // S)
+    return seg, -(-N // seg)
+
+
+def _topk_any(sim: torch.Tensor, k: int, gidx: Optional[torch.Tensor] = None, idx_base: int = 0):
+    return topk(sim, k, gidx, idx_base) if k <= 64 else topk_wide(sim, k, gidx, idx_base)
+
+
+def segmented_sim_buffer(nq: int, N: int, device, S: Optional[int] = None) -> torch.Tensor:
+    """The score buffer `topk_segmented` takes: fp32 [nq, N] whose row stride is padded to a whole number of segments of
+    `search_segments(nq, N, S)` (pass it as `out=` to `sim_max_stream` or `sim_max`); the padding is never read as a score."""
+    seg, S = search_segments(nq, N, S)
+    return torch.empty((nq, seg * S), dtype=torch.float32, device=device)[:, :N]
+
+
+def topk_segmented(sim: torch.Tensor, k: int, S: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two-level top-k of sim [nq, N] (a `segmented_sim_buffer` of the same S): bit-identical to `topk` (k <= 64) / `topk_wide`
+    (k <= 256) on the same scores for every S, with nq S workgroups instead of nq.
+    Level 1: with the row stride a whole number of segments, segment s of query q is row q S + s of a matrix with ld = L, so one
+    call ranks all the equal-length segments; each query's last segment may be shorter and is ranked by a second call over the nq
+    rows of the buffer at column (S - 1) L with idx_base.  (The first call also walks those last segments as rows of length L:
+    their tails are the buffer's padding, and their candidates are replaced by the second call's.)
+    Level 2: the local indices become global, the S k candidates per query are merged by the same kernel on their global indices,
+    exactly as `dist.ShardedRanker.rank` merges the shards' candidates (unused slots: idx -1 -> 2^31 - 1 in, sim -inf -> idx -1 out)."""
+    nq, N = sim.shape
+    seg, S = search_segments(nq, N, S)
+    if S == 1:
+        return _topk_any(sim, k)
+    assert sim.dtype == torch.float32 and sim.stride(1) == 1 and sim.stride(0) == seg * S, "topk_segmented: sim must be a segmented_sim_buffer"
+    tail = N - (S - 1) * seg                                   # 1 .. seg
+    cv, ci = _topk_any(torch.as_strided(sim, (nq * S, seg), (seg, 1)), k)      # (the last row ends where the allocation ends)
+    cv, ci = cv.view(nq, S, k), ci.view(nq, S, k)
+    base = torch.arange(S, dtype=torch.int32, device=sim.device).mul_(seg).view(1, S, 1)
+    ci = torch.where(ci < 0, torch.full_like(ci, 2**31 - 1), ci + base)
+    if tail != seg:
+        tv, ti = _topk_any(sim[:, (S - 1) * seg:], k, None, (S - 1) * seg)
+        cv[:, S - 1], ci[:, S - 1] = tv, torch.where(ti < 0, torch.full_like(ti, 2**31 - 1), ti)
+    mv, mi = _topk_any(cv.view(nq, S * k), k, ci.view(nq, S * k).contiguous(), 0)
+    return mv, torch.where(torch.isinf(mv) & (mv < 0), torch.full_like(mi, -1), mi)
+
+
+def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Index search: the k best gallery rows for each query -> (vals [nq,k] fp32, idx [nq,k] int32), 1 <= k <= 256; the streaming
+    score kernel followed by the two-level top-k.  The result is bit-identical to `topk` / `topk_wide` on `sim_max_stream`'s scores
+    for every S (default: `search_segments`)."""
+    if not 1 <= k <= 256:
+        raise ValueError(f"search_topk: k={k} must be in [1,256]")
+    nq, N = fusion16.shape[0], feats16.shape[0]
+    sim = segmented_sim_buffer(nq, N, fusion16.device, S)
+    sim_max_stream(fusion16, feats16, out=sim)
+    return topk_segmented(sim, k, S)
+
+
 def rank_of(sim: torch.Tensor, listed: torch.Tensor) -> torch.Tensor:
     """Position of listed[q,l] in the stable order of row q (int32; -1 where listed < 0)."""
     lib = L.load()

@@ -3,7 +3,9 @@
 The reference re-encodes the whole gallery on every run (`src/utils.py:46-77` returns tensors that nobody persists;
 `save_memory` only moves them to the CPU, `:67-69`).  A gallery is encoded once here and kept as ONE safetensors file:
 
-    feats      [N, 32, 256]  fp32   unit-norm Q-Former query features (what `inference` ranks against)
+    feats      [N, 32, 256]  fp32   unit-norm Q-Former query features (what `inference` ranks against); or fp16 / bf16
+                                    (`feats_dtype`): exactly the bits a 16-bit rank dtype ranks on (`model.similarity` rounds
+                                    before `sim_max`) and the operand `sprc_amd.search` streams, at half the bytes
     raw        [N, 257, D]   fp32, or the engine's 16-bit operand dtype (`raw_dtype`)
                                     optional: ViT embeddings of the images that can be *reference* images of a query
                                     (CIRR/FashionIQ take references from the gallery itself); omitted for pure galleries.
@@ -29,12 +31,15 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 FORMAT = "sprc-index-1"
+_DTYPE_NAMES = {torch.float16: "fp16", torch.bfloat16: "bf16"}
 
 
 def save_index(path, feats: torch.Tensor, names: Sequence[str], raw: Optional[torch.Tensor] = None, backbone: str = "",
                compute_dtype: str = "", checkpoint_sha256: str = "", raw_dtype: torch.dtype = torch.float32,
-               raw_names: Optional[Sequence[str]] = None) -> None:
-    """raw_names: `raw` holds the embeddings of these gallery images only (one row each, in this order)."""
+               raw_names: Optional[Sequence[str]] = None, feats_dtype: torch.dtype = torch.float32) -> None:
+    """raw_names: `raw` holds the embeddings of these gallery images only (one row each, in this order).
+    feats_dtype: float16 / bfloat16 store `feats` rounded to that dtype (recorded as `feats_dtype` in the metadata); the default
+    writes the fp32 file this format has always had, without the key."""
     from safetensors.torch import save_file
     if feats.dim() != 3 or feats.shape[1] != 32:
         raise ValueError(f"feats must be [N,32,E], got {tuple(feats.shape)}")
@@ -44,7 +49,9 @@ def save_index(path, feats: torch.Tensor, names: Sequence[str], raw: Optional[to
         raise ValueError("raw_names must name gallery rows whose embeddings are given in `raw`")
     if len(set(names)) != len(names):
         raise ValueError("gallery names must be unique (they are the join key of the relative datasets)")
-    tensors = {"feats": feats.detach().to("cpu", torch.float32).contiguous()}
+    if feats_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"feats_dtype {feats_dtype}")
+    tensors = {"feats": feats.detach().to(feats_dtype).to("cpu").contiguous()}         # rounded where the tensor lives, then copied
     if raw is not None:
         if raw_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise ValueError(f"raw_dtype {raw_dtype}")
@@ -53,14 +60,19 @@ def save_index(path, feats: torch.Tensor, names: Sequence[str], raw: Optional[to
             "checkpoint_sha256": checkpoint_sha256}
     if raw_names is not None:
         meta["raw_names"] = json.dumps(list(raw_names))
+    if feats_dtype != torch.float32:
+        meta["feats_dtype"] = _DTYPE_NAMES[feats_dtype]
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     save_file(tensors, str(path), metadata=meta)
 
 
-def load_index(path, device="cpu", with_raw: bool = True) -> Tuple[Tuple[torch.Tensor, Optional[torch.Tensor]], List[str], dict]:
+def load_index(path, device="cpu", with_raw: bool = True,
+               keep_feats_dtype: bool = False) -> Tuple[Tuple[torch.Tensor, Optional[torch.Tensor]], List[str], dict]:
     """-> ((feats, raw or None), names, metadata) with the tensors on `device`: the `(index_features, index_names)` pair
-    the reference's `compute_*_val_metrics` / `generate_*_predictions` take."""
+    the reference's `compute_*_val_metrics` / `generate_*_predictions` take.  `feats` comes back as fp32 (a 16-bit store is
+    upcast after the copy to `device`) unless keep_feats_dtype, which hands back the stored dtype; a file without `feats_dtype`
+    in its metadata is an fp32 store."""
     from safetensors import safe_open
     with safe_open(str(path), framework="pt", device="cpu") as f:
         meta = f.metadata() or {}
@@ -71,7 +83,12 @@ def load_index(path, device="cpu", with_raw: bool = True) -> Tuple[Tuple[torch.T
     names = json.loads(meta["names"])
     if len(names) != feats.shape[0]:
         raise ValueError(f"{path}: {len(names)} names for {feats.shape[0]} rows")
+    stored = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(meta.get("feats_dtype"), torch.float32)
+    if feats.dtype != stored:
+        raise ValueError(f"{path}: feats are {feats.dtype}, the metadata says {stored}")
     feats = feats.to(device)
+    if not keep_feats_dtype:
+        feats = feats.float()
     raw = raw.to(device).float() if raw is not None else None
     if raw is not None and "raw_names" in meta:
         from .harness import RawStore

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Index search against its alternatives on one GPU, in one process, arms alternating inside every repetition (HIP events):
+
+  (a) stream   E.search_topk: sprc_sim_max_stream + two-level top-k              (fp16 gallery)
+  (a1) ..sim   its score kernel alone -> the achieved gallery bytes / s
+  (b) gemm16   E.topk(E.sim_max(q16, g16), k): the 16-bit GEMM path + one-level top-k
+  (b2) gemm16+2lvl  E.sim_max into a segmented buffer + E.topk_segmented (what Searcher runs above its nq threshold)
+  (c) gemm32   fp32 sim_max + topk (the default rank_dtype); skipped when the fp32 gallery does not fit --fp32-budget-gb
+  (d) copy     torch device-to-device copy of the fp16 gallery bytes (read + write): the box's streaming rate
+
+    python tools/search_bench.py [--sizes 2297,123403,1000000] [--nq 1,8,32,64,256] [-k 50] [--reps 20] [--warmup 3] [--out FILE]
+
+Synthetic unit-norm gallery and queries.  Per (N, nq): median [min .. max] microseconds per arm over the repetitions, the spread
+of (a) and (b), and for (a1) / (d) the bytes / s.
+
+    python tools/search_bench.py --query-split [--sizes 123403] [--reps 10]
+
+Report only: one whole `Searcher` query on the full-depth synthetic ViT-g model (fp16 engine), split into reference embeddings (a stored
+name: a lookup; an image file: decode + transform + ViT), fuse and rank, each phase ended by a device synchronisation."""
+import argparse
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from sprc_amd import engine as E  # noqa: E402
+
+
+def _unit(x):
+    return x / x.norm(dim=-1, keepdim=True)
+
+
+def _gallery(N, gen, dev, chunk=65536):
+    g = torch.empty((N, 32, 256), dtype=torch.float16, device=dev)
+    for s in range(0, N, chunk):
+        n = min(chunk, N - s)
+        g[s:s + n] = _unit(torch.randn((n, 32, 256), generator=gen, device=dev)).to(torch.float16)
+    return g
+
+
+def _time(arms, reps, warmup):
+    """arms: {name: fn}; every repetition runs every arm once, in order -> {name: [ms, ...]}"""
+    out = {n: [] for n in arms}
+    for r in range(warmup + reps):
+        for name, fn in arms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if r >= warmup:
+                out[name].append(a.elapsed_time(b))
+    return out
+
+
+def _fmt(ms):
+    return f"{statistics.median(ms) * 1e3:9.1f} [{min(ms) * 1e3:8.1f} .. {max(ms) * 1e3:8.1f}]"
+
+
+def _clock():
+    try:
+        import subprocess
+        r = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=20).stdout
+        return " | ".join(l.strip() for l in r.splitlines() if "sclk" in l or "mclk" in l)[:300]
+    except Exception as e:       # the reading is optional
+        return f"(no clock reading: {e})"
+
+
+def query_split(a, say):
+    import tempfile
+    import numpy as np
+    from PIL import Image
+    from sprc_amd import synth
+    from sprc_amd.blip_validate import model_fingerprint
+    from sprc_amd.index import save_index
+    from sprc_amd.model import get_model_class
+    from sprc_amd.search import Searcher
+    dev = "cuda:0"
+    model = get_model_class("blip2_cir_align_prompt").from_pretrained(model_type="pretrain", compute_dtype="fp16", device=dev)
+    model.init_synthetic(seed=1)
+    feats, raw = model.extract_target_features(synth.make_images(2, seed=3).to(dev))
+    ids, mask, _ = synth.make_queries(1, 2, seed=4)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        save_index(f"{tmp}/s.safetensors", feats, ["a", "b"], raw=raw, checkpoint_sha256=model_fingerprint(model), raw_dtype=torch.float16,
+                   feats_dtype=torch.float16)
+        Image.fromarray(np.random.default_rng(0).integers(0, 256, size=(375, 500, 3), dtype=np.uint8)).save(f"{tmp}/q.png")
+        s = Searcher(model, f"{tmp}/s.safetensors")
+        for N in [int(x) for x in a.sizes.split(",")]:
+            s.feats = _gallery(N, gen, dev)
+            for what, ref in (("stored reference", ["a"]), ("image file (500 x 375 PNG)", [Path(f"{tmp}/q.png")])):
+                rows = []
+                for r in range(a.warmup + a.reps):
+                    t = {}
+                    s.search_ids(ref, ids, mask, a.k, timings=t)
+                    if r >= a.warmup:
+                        rows.append(t)
+                med = {k: statistics.median(x[k] for x in rows) for k in rows[0]}
+                say(f"query split, N = {N}, k = {a.k}, {what}: reference {med['reference_ms']:.3f} ms, fuse {med['fuse_ms']:.3f} ms, rank {med['rank_ms']:.3f} ms "
+                    f"(medians of {a.reps}; host wall time per phase, device idle at each boundary)")
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--query-split", action="store_true")
+    p.add_argument("--sizes", default="2297,123403,1000000")
+    p.add_argument("--nq", default="1,8,32,64,256")
+    p.add_argument("-k", type=int, default=50)
+    p.add_argument("--reps", type=int, default=20)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--fp32-budget-gb", type=float, default=40.0)
+    p.add_argument("--out", default=None)
+    a = p.parse_args(argv)
+    dev = "cuda:0"
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"search_bench: k={a.k} reps={a.reps} warmup={a.warmup}  device={torch.cuda.get_device_name(0)}  times in us: median [min .. max]")
+    say(f"clocks: {_clock()}")
+    if a.query_split:
+        query_split(a, say)
+        if a.out:
+            Path(a.out).write_text("\n".join(lines) + "\n")
+        return lines
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N in [int(x) for x in a.sizes.split(",")]:
+        g16 = _gallery(N, gen, dev)
+        gbytes = g16.numel() * 2
+        with_c = gbytes * 2 <= a.fp32_budget_gb * 2**30
+        g32 = g16.float() if with_c else None
+        dst = torch.empty_like(g16)
+        say(f"\nN = {N}  ({gbytes / 2**20:.0f} MiB fp16)" + ("" if with_c else "  [arm (c) skipped: the fp32 gallery exceeds --fp32-budget-gb]"))
+        for nq in [int(x) for x in a.nq.split(",")]:
+            q16 = _unit(torch.randn((nq, 256), generator=gen, device=dev)).to(torch.float16).contiguous()
+            q32 = q16.float()
+            sim_a = torch.empty((nq, N), dtype=torch.float32, device=dev)
+            sim_b = torch.empty((nq, N), dtype=torch.float32, device=dev)
+            sim_s = E.segmented_sim_buffer(nq, N, dev)
+            arms = {
+                "a": lambda: E.search_topk(q16, g16, a.k),
+                "a1": lambda: E.sim_max_stream(q16, g16, out=sim_a),
+                "b": lambda: E.topk(E.sim_max(q16, g16, out=sim_b), a.k),
+                "b2": lambda: E.topk_segmented(E.sim_max(q16, g16, out=sim_s), a.k),
+                "d": lambda: dst.copy_(g16),
+            }
+            if with_c:
+                arms["c"] = lambda: E.topk(E.sim_max(q32, g32, out=sim_b), a.k)
+            t = _time(arms, a.reps, a.warmup)
+            va, ia = E.search_topk(q16, g16, a.k)
+            vb, ib = E.topk(E.sim_max_stream(q16, g16), a.k)
+            assert torch.equal(ia, ib) and torch.equal(va, vb)
+            ma, mb = statistics.median(t["a"]), statistics.median(t["b"])
+            spread = max(max(t["a"]) - min(t["a"]), max(t["b"]) - min(t["b"]))
+            seg, S = E.search_segments(nq, N)
+            say(f"  nq={nq:4d} S={S:3d}  (a) stream+2lvl {_fmt(t['a'])}   (b) gemm16+topk {_fmt(t['b'])}   (b2) gemm16+2lvl {_fmt(t['b2'])}"
+                + (f"   (c) gemm32+topk {_fmt(t['c'])}" if with_c else ""))
+            say(f"           b/a = {mb / ma:5.2f}  (a faster by {(mb - ma) * 1e3:8.1f} us; spread of the two arms {spread * 1e3:7.1f} us)"
+                f"   (a1) stream kernel {_fmt(t['a1'])} = {gbytes / statistics.median(t['a1']) / 1e9:6.2f} TB/s gallery"
+                f"   (d) copy {_fmt(t['d'])} = {gbytes / statistics.median(t['d']) / 1e9:6.2f} TB/s read (+ as much written)")
+            del sim_a, sim_b, sim_s
+        del g16, g32, dst
+        torch.cuda.empty_cache()
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text("\n".join(lines) + "\n")
+    return lines
+
+
+if __name__ == "__main__":
+    main()
