@@ -254,6 +254,16 @@ int sprc_sim_max(const void* fusion, const void* feats, float* sim, int64_t ld_s
 int sprc_sim_max_stream(const void* fusion, const void* feats, float* sim, int64_t ld_sim,
                         int32_t nq, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
 
+/* sprc_sim_max_stream through a row list (filtered index search): sim[q, m] = max_j <fusion[q,:], feats[rows[m], j, :]> for m in [0, M);
+ * the output is COMPACT, M columns.  rows: DEVICE int32 [M], any order, repeats allowed; a value outside [0, N) is clamped into it by
+ * the kernel (no list content can address outside feats -- a defence, not an interface: callers pass valid rows).  The contract is
+ * sprc_sim_max_stream's (1 <= nq <= 32, E == 256, SPRC_F16 | SPRC_BF16, 16-byte aligned fusion and feats) plus rows != NULL, M >= 1,
+ * ld_sim >= M, N >= 1; anything else is SPRC_EINVAL before any launch.  Writes sim[q, 0..M) for q < nq and nothing else; allocates
+ * nothing, does not synchronise.  The per-image instruction sequence is sprc_sim_max_stream's, so sim[q, m] is bit-identical to that
+ * function's sim[q, rows[m]] for any data.  Same ABI version: a symbol added, nothing changed. */
+int sprc_sim_max_stream_rows(const void* fusion, const void* feats, const int32_t* rows, float* sim, int64_t ld_sim,
+                             int32_t nq, int32_t M, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
+
 /* Per row of sim[nq,N] (ld in elements): the k smallest keys (fl32(1 - sim[n]), gidx[n]) ascending,
  * i.e. the first k entries of a STABLE argsort of the fp32 distance (the ranking contract,
  * SURVEY.md section 7).  gidx: optional int32 [nq,N] global indices (NULL -> n + idx_base).

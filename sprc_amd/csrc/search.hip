@@ -1,4 +1,4 @@
-// search.hip -- index search: streaming small-batch scoring (sprc_sim_max_stream).
+// search.hip -- index search: streaming small-batch scoring (sprc_sim_max_stream) and its row-list form (sprc_sim_max_stream_rows).
 //
 // sim[q, n] = max_j <fusion[q,:], feats[n,j,:]> for 1 <= nq <= 32 queries against a gallery that is read from HBM exactly once:
 // 16 KiB per image (16-bit), 2 * 32 * 256 * nq flops per image -- at nq = 1 almost no arithmetic per byte.  sprc_sim_max runs this
@@ -90,6 +90,66 @@ __global__ __launch_bounds__(256, 2) void sim_max_stream_kernel(const char* __re
     if (r < nq && n + h < N) out[n] = h ? m1 : m0;
 }
 
+// ---- the same walk through a row list (sprc_sim_max_stream_rows): position m of the list takes image rows[m] ------------------------
+// The loop is sim_max_stream_kernel's (one image per wave per 16 MFMAs, two images held, the next pair's loads behind the current
+// pair's MFMAs, peeled last trip, no LDS, no barrier) and the per-image chain is the same stream_dot, so sim[q, m] has the bits of
+// the plain kernel's sim[q, rows[m]].  What is new is that a load's address depends on a value from memory.  The wave's two row
+// indices of trip t + 2 are fetched while trip t computes and are first looked at in trip t + 1, whose loads they address: the fetch
+// never sits between an MFMA chain and the loads behind it.  They are two 4-byte vector loads in the same in-order vmcnt queue as
+// the operand loads, so their wait is one of the counted waits the MFMAs need anyway.  (Written as relaxed wave-scope atomic loads,
+// which compile to plain global_load_dword: an ordinary load of a value that is only used a trip later is sunk by hipcc behind the
+// trip's conditional store, to the loop's end, and waited for at once.)  The position is clamped to M - 1 and the row VALUE to
+// [0, N - 1]: no list content addresses outside feats, and no load is predicated.
+__device__ __forceinline__ int stream_row_ahead(const int32_t* rows, int m, int M) {
+    return __hip_atomic_load(rows + min(m, M - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+__device__ __forceinline__ int stream_row_clamp(int row, int N) { return min(max(row, 0), N - 1); }
+
+__device__ __forceinline__ void stream_load_row(u32x4 (&a)[16], const char* feats, int lane_off, int row) {
+    const u32x4* p = reinterpret_cast<const u32x4*>(feats + (int64_t)row * STREAM_IMG_BYTES + lane_off);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) a[t] = p[2 * t];
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void sim_max_stream_rows_kernel(const char* __restrict__ fusion, const char* __restrict__ feats,
+                                                                     const int32_t* __restrict__ rows, float* __restrict__ sim, int64_t ld,
+                                                                     int nq, int M, int N, int trips) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    u32x4 q[16];
+    {
+        const u32x4* p = reinterpret_cast<const u32x4*>(fusion + (int64_t)min(r, nq - 1) * (STREAM_E * 2) + h * 16);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const u32x4 v = p[2 * t];
+            q[t] = r < nq ? v : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    const int t0 = (int)((int64_t)blockIdx.x * trips / gridDim.x), t1 = (int)((int64_t)(blockIdx.x + 1) * trips / gridDim.x);
+    if (t0 >= t1) return;
+    const int lane_off = r * (STREAM_E * 2) + h * 16;
+    float* out = sim + (int64_t)r * ld + h;          // lane (r, h) stores position m + h of its pair
+    int m = t0 * STREAM_P + 2 * wave;                // first list position of this wave's pair in the current trip
+    u32x4 a0[16], a1[16];
+    stream_load_row(a0, feats, lane_off, stream_row_clamp(rows[min(m, M - 1)], N));
+    stream_load_row(a1, feats, lane_off, stream_row_clamp(rows[min(m + 1, M - 1)], N));
+    int n0 = rows[min(m + STREAM_P, M - 1)], n1 = rows[min(m + STREAM_P + 1, M - 1)];      // the next trip's rows, as fetched
+    for (int trip = t0; trip + 1 < t1; ++trip, m += STREAM_P) {
+        const int j0 = stream_row_clamp(n0, N), j1 = stream_row_clamp(n1, N);                // fetched a trip ago
+        n0 = stream_row_ahead(rows, m + 2 * STREAM_P, M), n1 = stream_row_ahead(rows, m + 2 * STREAM_P + 1, M);
+        const f32x16 c0 = stream_dot<F16>(a0, q);
+        stream_load_row(a0, feats, lane_off, j0);
+        const f32x16 c1 = stream_dot<F16>(a1, q);
+        stream_load_row(a1, feats, lane_off, j1);
+        const float m0 = stream_rowmax(c0), m1 = stream_rowmax(c1);
+        if (r < nq && m + h < M) out[m] = h ? m1 : m0;
+    }
+    const float m0 = stream_rowmax(stream_dot<F16>(a0, q)), m1 = stream_rowmax(stream_dot<F16>(a1, q));
+    if (r < nq && m + h < M) out[m] = h ? m1 : m0;
+}
+
 }  // namespace sprc
 
 using namespace sprc;
@@ -113,5 +173,30 @@ extern "C" int sprc_sim_max_stream(const void* fusion, const void* feats, float*
     else
         hipLaunchKernelGGL(sim_max_stream_kernel<false>, dim3(grid), dim3(256), 0, st, f, g, sim, ld_sim, nq, N, trips);
     SPRC_CHECK_LAUNCH("sprc_sim_max_stream");
+    return SPRC_OK;
+}
+
+extern "C" int sprc_sim_max_stream_rows(const void* fusion, const void* feats, const int32_t* rows, float* sim, int64_t ld_sim, int32_t nq,
+                                        int32_t M, int32_t N, int32_t E, int32_t dtype, sprc_stream s) {
+    SPRC_REQUIRE(fusion && feats && rows && sim, "sprc_sim_max_stream_rows: null pointer");
+    SPRC_REQUIRE(nq >= 1 && nq <= 32, "sprc_sim_max_stream_rows: nq=%d must be in [1,32] (walk more queries in blocks of 32)", nq);
+    SPRC_REQUIRE(E == STREAM_E, "sprc_sim_max_stream_rows: E=%d must be %d", E, STREAM_E);
+    SPRC_REQUIRE(dtype == SPRC_F16 || dtype == SPRC_BF16, "sprc_sim_max_stream_rows: dtype %d must be SPRC_F16 or SPRC_BF16", dtype);
+    SPRC_REQUIRE(N >= 1 && M >= 1 && M <= INT32_MAX - 4 * STREAM_P && ld_sim >= M, "sprc_sim_max_stream_rows: bad shape M=%d N=%d ld_sim=%lld", M, N,
+                 (long long)ld_sim);
+    SPRC_REQUIRE(((uintptr_t)fusion & 15) == 0 && ((uintptr_t)feats & 15) == 0 && ((uintptr_t)rows & 3) == 0,
+                 "sprc_sim_max_stream_rows: fusion and feats must be 16-byte aligned, rows 4-byte aligned");
+    hipStream_t st = (hipStream_t)s;
+    const int trips = (int)(((int64_t)M + STREAM_P - 1) / STREAM_P);
+    const int grid = min(trips, STREAM_WG_PER_CU * stream_cus(st));
+    ProfScope prof(SPRC_K_RANK, st, 2.0 * nq * (double)M * 32.0 * E,
+                   (double)M * (STREAM_IMG_BYTES + 4) + (double)nq * E * 2.0 + (double)nq * M * 4.0);
+    const char* f = (const char*)fusion;
+    const char* g = (const char*)feats;
+    if (dtype == SPRC_F16)
+        hipLaunchKernelGGL(sim_max_stream_rows_kernel<true>, dim3(grid), dim3(256), 0, st, f, g, rows, sim, ld_sim, nq, M, N, trips);
+    else
+        hipLaunchKernelGGL(sim_max_stream_rows_kernel<false>, dim3(grid), dim3(256), 0, st, f, g, rows, sim, ld_sim, nq, M, N, trips);
+    SPRC_CHECK_LAUNCH("sprc_sim_max_stream_rows");
     return SPRC_OK;
 }

@@ -234,21 +234,31 @@ STREAM_WG_PER_CU = 2        # its grid: min(ceil(N / STREAM_P), STREAM_WG_PER_CU
 STREAM_MAX_NQ = 32          # queries of one launch (the columns of one MFMA tile)
 
 
-def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`sim_max` for few queries against a stored 16-bit gallery (sprc_sim_max_stream: the gallery is streamed from HBM once, no
-    LDS); fusion [nq,256], feats [N,32,256], both fp16 or both bf16.  More than 32 queries are walked in blocks of 32 into one sim."""
+    LDS); fusion [nq,256], feats [N,32,256], both fp16 or both bf16.  More than 32 queries are walked in blocks of 32 into one sim.
+    rows (optional): int32 device tensor [M] of gallery rows -> the COMPACT scores [nq, M], column m the score of image rows[m]
+    (sprc_sim_max_stream_rows: only the listed images are read; bit-identical to the columns `rows` of the call without it)."""
     lib = L.load()
     nq, E = fusion.shape
     N, J, E2 = feats.shape
     assert J == 32 and E2 == E and fusion.dtype == feats.dtype and fusion.is_contiguous() and feats.is_contiguous()
     dt = _SPRC_DT[fusion.dtype]
+    if rows is not None:
+        assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.device == feats.device
+    W = N if rows is None else rows.shape[0]
     if out is None:
-        out = torch.empty((nq, N), dtype=torch.float32, device=fusion.device)
-    assert out.dtype == torch.float32 and out.shape == (nq, N) and (N == 1 or out.stride(1) == 1)
+        out = torch.empty((nq, W), dtype=torch.float32, device=fusion.device)
+    assert out.dtype == torch.float32 and out.shape == (nq, W) and (W == 1 or out.stride(1) == 1)
     for q0 in range(0, max(nq, 1), STREAM_MAX_NQ):
         nb = min(STREAM_MAX_NQ, nq - q0)
-        L.check(lib.sprc_sim_max_stream(fusion[q0:].data_ptr(), feats.data_ptr(), out[q0:].data_ptr(), out.stride(0), nb, N, E, dt,
-                                        _stream()), "sprc_sim_max_stream")
+        if rows is None:
+            L.check(lib.sprc_sim_max_stream(fusion[q0:].data_ptr(), feats.data_ptr(), out[q0:].data_ptr(), out.stride(0), nb, N, E, dt,
+                                            _stream()), "sprc_sim_max_stream")
+        else:
+            L.check(lib.sprc_sim_max_stream_rows(fusion[q0:].data_ptr(), feats.data_ptr(), rows.data_ptr(), out[q0:].data_ptr(), out.stride(0),
+                                                 nb, W, N, E, dt, _stream()), "sprc_sim_max_stream_rows")
     return out
 
 
@@ -306,16 +316,48 @@ def topk_segmented(sim: torch.Tensor, k: int, S: Optional[int] = None) -> Tuple[
     return mv, torch.where(torch.isinf(mv) & (mv < 0), torch.full_like(mi, -1), mi)
 
 
-def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Optional[int] = None, rows: Optional[torch.Tensor] = None,
+                exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Index search: the k best gallery rows for each query -> (vals [nq,k] fp32, idx [nq,k] int32), 1 <= k <= 256; the streaming
     score kernel followed by the two-level top-k.  The result is bit-identical to `topk` / `topk_wide` on `sim_max_stream`'s scores
-    for every S (default: `search_segments`)."""
+    for every S (default: `search_segments`).
+
+    Filtered search.  rows: int32 device tensor [M] -- only these gallery rows are scored (and read) and ranked; the two-level top-k
+    runs on the M compact scores (`search_segments(nq, M, S)`) and the returned indices are gallery rows.  The list must be STRICTLY
+    ASCENDING with values in [0, N): then the tie rule (distance, compact position) is the rule (distance, gallery row).  It is
+    validated where it is made (`search.resolve_rows`), not here: a tensor handed to this function is trusted.
+    exclude: int32 tensor [nq] of gallery rows, negative for none -- that row's score is set to -inf for that query on the device
+    before the top-k (at its compact position when `rows` is given; a row that is not listed excludes nothing).
+    With either argument, positions beyond the number of admissible images come back as score -inf and index -1 for every S.
+    With neither, the function does exactly what it did without them."""
     if not 1 <= k <= 256:
         raise ValueError(f"search_topk: k={k} must be in [1,256]")
     nq, N = fusion16.shape[0], feats16.shape[0]
-    sim = segmented_sim_buffer(nq, N, fusion16.device, S)
-    sim_max_stream(fusion16, feats16, out=sim)
-    return topk_segmented(sim, k, S)
+    if rows is None and exclude is None:
+        sim = segmented_sim_buffer(nq, N, fusion16.device, S)
+        sim_max_stream(fusion16, feats16, out=sim)
+        return topk_segmented(sim, k, S)
+    dev = fusion16.device
+    M = N if rows is None else int(rows.shape[0])
+    if M < 1:
+        raise ValueError("search_topk: an empty row list")
+    sim = segmented_sim_buffer(nq, M, dev, S)
+    sim_max_stream(fusion16, feats16, out=sim, rows=rows)
+    if exclude is not None:
+        exclude = exclude.to(device=dev, dtype=torch.int32)
+        if exclude.shape != (nq,):
+            raise ValueError(f"search_topk: exclude must be [nq]={nq}, got {tuple(exclude.shape)}")
+        if rows is None:
+            pos, hit = exclude.clamp(0, M - 1).long(), (exclude >= 0) & (exclude < M)
+        else:
+            pos = torch.searchsorted(rows, exclude.contiguous()).clamp_(max=M - 1)
+            hit = rows[pos] == exclude                          # (a negative value is never listed)
+        q = torch.arange(nq, device=dev)
+        sim[q, pos] = torch.where(hit, torch.full_like(sim[q, pos], float("-inf")), sim[q, pos])
+    vals, idx = topk_segmented(sim, k, S)
+    if rows is not None:
+        idx = rows[idx.clamp_(min=0)]                           # compact position -> gallery row (unused slots: fixed below)
+    return vals, torch.where(torch.isneginf(vals), -1, idx)
 
 
 def rank_of(sim: torch.Tensor, listed: torch.Tensor) -> torch.Tensor:

@@ -4,24 +4,34 @@
     python -m sprc_amd.search build --images DIR --model-path X --out STORE [--backbone B --dtype fp16 --feats-dtype fp16
                                     --keep-raw all|none --gpu-preprocess]
     python -m sprc_amd.search query --index STORE --model-path X (--reference NAME | --reference-image FILE) --caption "..."
-                                    [-k 10] [--json]
+                                    [-k 10] [--json] [--within-file FILE | --within-glob PATTERN] [--exclude NAME...]
+                                    [--exclude-reference]
+    python -m sprc_amd.search add    --index STORE --images DIR --model-path X [--out STORE2]     (encodes the new stems only)
+    python -m sprc_amd.search remove --index STORE --names NAME... [--out STORE2]
 
     s = Searcher(model, "gallery.safetensors")
     s.search(["dog-017", "/tmp/photo.jpg"], ["the same dog on a beach", "make it night"], k=10)
+    shoes = s.subset(n for n in s.names if n.startswith("shoes/"))                  # uploaded once
+    s.search(["dog-017"], ["in red"], k=10, within=shoes, exclude_reference=True)
 
 No reference counterpart: the reference ranks inside its evaluation loops only (validate_blip.py:253-254).  The pieces are the
 evaluation path's own -- caption processor, tokenizer, `model.fuse` -- followed by `engine.search_topk` on the store's 16-bit
 `feats`: the streaming score kernel (csrc/search.hip) and the two-level top-k.  The gallery is uploaded once, when the Searcher
 is made; a search does no per-gallery-item work on the host.
+
+A filtered search (`within=`, `exclude=`, `exclude_reference=`, or after `remove`) ranks a row list instead of the whole gallery:
+`engine.search_topk(rows=, exclude=)` on sprc_sim_max_stream_rows reads the listed images only.  The list is built and validated
+on the host once (`resolve_rows`; `Searcher.subset` keeps it on the device for repeated searches); nothing else is per item.
 """
 from __future__ import annotations
 
+import fnmatch
 import json
 import os
 import time
 from argparse import ArgumentParser
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -39,17 +49,72 @@ MODEL_NAME = "blip2_cir_align_prompt"            # the command line's model clas
 
 class _RawRows:
     """name -> raw ViT embeddings of a stored gallery image (a stacked tensor or a `harness.RawStore`), None when not kept:
-    the mapping `harness._stack_refs` takes."""
+    the mapping `harness._stack_refs` takes.  `extra`: the embeddings of rows added after the store was loaded, by row."""
 
     def __init__(self, raw, row_of: Dict[str, int]):
-        self.raw, self.row_of = raw, row_of
+        self.raw, self.row_of, self.extra = raw, row_of, {}
 
     def get(self, name):
         i = self.row_of.get(name)
-        return None if i is None or self.raw is None else self.raw[i]
+        if i is None:
+            return None
+        if i in self.extra:
+            return self.extra[i]
+        return None if self.raw is None or i >= len(self.raw) else self.raw[i]
 
     def __getitem__(self, name):
-        return self.raw[self.row_of[name]]
+        r = self.get(name)
+        if r is None:
+            raise KeyError(name)
+        return r
+
+
+def resolve_rows(within, n_rows: int, row_of: Dict[str, int], exclude: Iterable[str] = (), removed=frozenset()) -> torch.Tensor:
+    """The row list of a filtered search -> int32 CPU tensor, strictly ascending, values in [0, n_rows): what `engine.search_topk(rows=)`
+    trusts.  Host work only, before any device call.
+    within: None (every row), an iterable of gallery names (sorted and de-duplicated here; an unknown name raises KeyError), or rows
+    as an integer tensor / list of ints, which must already be strictly ascending and in range (ValueError otherwise).
+    exclude: names whose rows are taken out (unknown: KeyError); removed: rows taken out.  An empty result raises ValueError."""
+    if within is None:
+        rows = list(range(n_rows))
+    else:
+        if isinstance(within, torch.Tensor):
+            if within.dim() != 1 or within.is_floating_point() or within.is_complex() or within.dtype == torch.bool:
+                raise ValueError(f"within: a tensor of rows must be one-dimensional and of an integer dtype, got {tuple(within.shape)} {within.dtype}")
+            items = within.cpu().tolist()
+        else:
+            if isinstance(within, (str, bytes)):
+                raise TypeError("within: an iterable of names or rows, not one string")
+            items = list(within)
+        if items and all(isinstance(i, int) and not isinstance(i, bool) for i in items):
+            if items[0] < 0 or items[-1] >= n_rows or any(b <= a for a, b in zip(items, items[1:])):
+                raise ValueError(f"within: rows must be strictly ascending values in [0, {n_rows})")
+            rows = items
+        else:
+            unknown = [n for n in items if not isinstance(n, str) or n not in row_of]
+            if unknown:
+                raise KeyError(f"within: not a gallery name of this index: {unknown[:3]}")
+            rows = sorted({row_of[n] for n in items})
+    exclude = [exclude] if isinstance(exclude, str) else list(exclude or ())
+    unknown = [n for n in exclude if n not in row_of]
+    if unknown:
+        raise KeyError(f"exclude: not a gallery name of this index: {unknown[:3]}")
+    out = {row_of[n] for n in exclude} | set(removed)
+    if out:
+        rows = [i for i in rows if i not in out]
+    if not rows:
+        raise ValueError("the filter leaves no gallery image to rank")
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+class Subset:
+    """A validated row list kept on the device (`Searcher.subset`): `within=` takes it for repeated searches of one subset."""
+
+    def __init__(self, rows_cpu: torch.Tensor, rows: torch.Tensor, edits: int):
+        self.rows_cpu, self.rows, self.edits = rows_cpu, rows, edits
+
+    def __len__(self):
+        return int(self.rows_cpu.shape[0])
 
 
 class Searcher:
@@ -78,6 +143,9 @@ class Searcher:
         self.names: List[str] = list(names)
         self.meta = meta
         self._raw = _RawRows(raw, {n: i for i, n in enumerate(self.names)})
+        self._removed: set = set()               # tombstoned rows: `names` keeps its numbering
+        self._edits = 0                          # bumped by add / remove: device row lists made before are rebuilt
+        self._live: Optional[Subset] = None      # every row that is not removed (made when the first row is removed)
         if preprocess is None:
             from .data_utils import targetpad_transform
             preprocess = targetpad_transform(1.25, 224)
@@ -109,12 +177,100 @@ class Searcher:
                 raise KeyError(f"reference {r!r} is neither a gallery name of this index nor an image file")
         return out[0] if len(out) == 1 else torch.cat(out)
 
+    # ---- row lists --------------------------------------------------------------------------------------
+    @property
+    def row_of(self) -> Dict[str, int]:
+        return self._raw.row_of
+
+    def subset(self, within) -> Subset:
+        """Resolve names (or rows) once and upload the list: the handle `within=` takes for repeated searches of the same subset."""
+        rows = resolve_rows(within, len(self.names), self.row_of, removed=self._removed)
+        return Subset(rows, rows.to(self.model.device), self._edits)
+
+    def _rows(self, within, exclude) -> Optional[torch.Tensor]:
+        """The device row list of one search, None for the whole gallery."""
+        if isinstance(within, Subset) and not exclude:
+            if within.edits != self._edits:                  # rows were added or removed since: drop the tombstones, upload again
+                within.rows_cpu = resolve_rows(within.rows_cpu, len(self.names), self.row_of, removed=self._removed)
+                within.rows, within.edits = within.rows_cpu.to(self.model.device), self._edits
+            return within.rows
+        if isinstance(within, Subset):
+            within = within.rows_cpu
+        if within is None and not exclude:
+            if not self._removed:
+                return None
+            if self._live is None or self._live.edits != self._edits:
+                self._live = self.subset(None)
+            return self._live.rows
+        return resolve_rows(within, len(self.names), self.row_of, exclude or (), self._removed).to(self.model.device)
+
+    # ---- edits (in memory; `index.append_index` / `remove_from_index` edit the file) ------------------------
+    def remove(self, names: Iterable[str]) -> None:
+        """Tombstone rows: they leave every later result and can no longer be named; `names` keeps its numbering."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in self.row_of]
+        if unknown:
+            raise KeyError(f"remove: not a gallery name of this index: {unknown[:3]}")
+        if len(self._removed) + len(set(names)) >= len(self.names):
+            raise ValueError("remove: nothing would be left")
+        for n in set(names):
+            i = self.row_of.pop(n)
+            self._removed.add(i)
+            self._raw.extra.pop(i, None)
+        self._edits += 1
+
+    def add(self, names: Sequence[str], feats: torch.Tensor, raw: Optional[torch.Tensor] = None) -> None:
+        """Append encoded rows: feats [n,32,256] (rounded to the rank dtype), raw [n,tokens,D] (optional: the embeddings that let the
+        new images be references).  Names of the gallery, or given twice, are refused.  The device tensor grows by doubling."""
+        names = list(names)
+        if feats.dim() != 3 or feats.shape[0] != len(names) or tuple(feats.shape[1:]) != tuple(self.feats.shape[1:]):
+            raise ValueError(f"add: feats {tuple(feats.shape)} for {len(names)} names, the gallery holds rows of {tuple(self.feats.shape[1:])}")
+        if raw is not None and raw.shape[0] != len(names):
+            raise ValueError("add: one row of `raw` per name")
+        dup = [n for n in names if n in self.row_of] + sorted({n for n in names if names.count(n) > 1})
+        if dup:
+            raise ValueError(f"add: name(s) already in the gallery or given twice: {dup[:3]}")
+        if not names:
+            return
+        n0, n1 = self.feats.shape[0], self.feats.shape[0] + len(names)
+        buf = getattr(self, "_buf", None)
+        if buf is None or buf.data_ptr() != self.feats.data_ptr() or buf.shape[0] < n1:
+            buf = torch.empty((max(2 * n0, n1),) + tuple(self.feats.shape[1:]), dtype=self.feats.dtype, device=self.feats.device)
+            buf[:n0] = self.feats
+            self._buf = buf
+        buf[n0:n1] = feats.to(device=buf.device, dtype=buf.dtype)
+        self.feats = buf[:n1]
+        for j, n in enumerate(names):
+            self.row_of[n] = n0 + j
+            if raw is not None:
+                self._raw.extra[n0 + j] = raw[j].to(self.model.device).float()
+        self.names.extend(names)
+        self._edits += 1
+
+    @torch.no_grad()
+    def add_images(self, files: Sequence) -> List[str]:
+        """Encode image files (the gallery's transform, `model.extract_target_features`) and `add` them under their stems."""
+        from PIL import Image
+        files = [Path(f) for f in files]
+        names = [f.stem for f in files]
+        if not files:
+            return names
+        images = torch.stack([self.preprocess(Image.open(f)) for f in files])
+        with torch.cuda.device(self.model.device):
+            feats, raw = self.model.extract_target_features(images.to(self.model.device, torch.float32))
+            self.add(names, feats, raw)
+        return names
+
     # ---- search -------------------------------------------------------------------------------------
     @torch.no_grad()
     def search_ids(self, reference, input_ids: torch.Tensor, attention_mask: torch.Tensor, k: int,
-                   timings: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   timings: Optional[dict] = None, within=None, exclude: Optional[Iterable[str]] = None,
+                   exclude_reference: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (scores [B,k] fp32, gallery rows [B,k] int32; -inf / -1 beyond the gallery's size).  timings: a dict that receives
-        the milliseconds of the three phases (reference embeddings, fuse, rank), each ended by a device synchronisation."""
+        the milliseconds of the three phases (reference embeddings, fuse, rank), each ended by a device synchronisation.
+        within: names, rows (int tensor / list, strictly ascending) or a `subset` handle -- only these are ranked; exclude: names
+        left out for every query; exclude_reference: a query's reference is left out when it is a gallery name.  A filtered search
+        (any of the three, or rows removed earlier) runs `engine.search_topk(rows=, exclude=)` for any number of queries."""
         dev = self.model.device
 
         def lap(key, t0):
@@ -123,6 +279,14 @@ class Searcher:
                 timings[key] = (time.perf_counter() - t0) * 1e3
             return time.perf_counter()
 
+        if isinstance(reference, (str, Path, torch.Tensor)):
+            reference = [reference]
+        reference = list(reference)
+        rows = self._rows(within, exclude)                                   # host: raises before any device work
+        skip = None
+        if exclude_reference:
+            skip = [self.row_of.get(r, -1) if isinstance(r, str) else -1 for r in reference]
+            skip = torch.tensor(skip, dtype=torch.int32) if any(i >= 0 for i in skip) else None
         t = time.perf_counter()
         with torch.cuda.device(dev):
             ref = self.reference_embeds(reference)
@@ -132,7 +296,11 @@ class Searcher:
             fusion = self.model.fuse(ref, input_ids.to(dev), attention_mask.to(dev))
             fusion = fusion.to(self.rank_dtype).contiguous()
             t = lap("fuse_ms", t)
-            if fusion.shape[0] <= STREAM_MAX_QUERIES:
+            if rows is not None or skip is not None:
+                if skip is not None and skip.shape[0] != fusion.shape[0]:
+                    raise ValueError("exclude_reference: one reference per query is required")
+                vals, idx = E.search_topk(fusion, self.feats, k, rows=rows, exclude=skip)
+            elif fusion.shape[0] <= STREAM_MAX_QUERIES:
                 vals, idx = E.search_topk(fusion, self.feats, k)
             else:
                 sim = E.sim_max(fusion, self.feats, out=E.segmented_sim_buffer(fusion.shape[0], self.feats.shape[0], dev))
@@ -140,12 +308,14 @@ class Searcher:
             lap("rank_ms", t)
         return vals, idx
 
-    def search(self, reference, captions: Union[str, Sequence[str]], k: int = 10, timings: Optional[dict] = None) -> List[List[Tuple[str, float]]]:
+    def search(self, reference, captions: Union[str, Sequence[str]], k: int = 10, timings: Optional[dict] = None, within=None,
+               exclude: Optional[Iterable[str]] = None, exclude_reference: bool = False) -> List[List[Tuple[str, float]]]:
         if isinstance(captions, str):
             captions = [captions]
         text = [self.txt_processors["eval"](c) for c in captions]
         tok = self.model.tokenizer(text, padding="max_length", truncation=True, max_length=self.model.max_txt_len, return_tensors="pt")
-        vals, idx = self.search_ids(reference, tok.input_ids, tok.attention_mask, k, timings=timings)
+        vals, idx = self.search_ids(reference, tok.input_ids, tok.attention_mask, k, timings=timings, within=within, exclude=exclude,
+                                    exclude_reference=exclude_reference)
         vals, idx = vals.cpu().tolist(), idx.cpu().tolist()
         return [[(self.names[i], float(v)) for v, i in zip(vr, ir) if i >= 0] for vr, ir in zip(vals, idx)]
 
@@ -176,7 +346,21 @@ def _parser() -> ArgumentParser:
     q.add_argument("--caption", type=str, required=True)
     q.add_argument("-k", type=int, default=10)
     q.add_argument("--json", action="store_true")
+    within = q.add_mutually_exclusive_group()
+    within.add_argument("--within-file", type=str, help="rank only the gallery names listed in this file, one per line")
+    within.add_argument("--within-glob", type=str, help="rank only the gallery names that match this pattern (fnmatch)")
+    q.add_argument("--exclude", type=str, nargs="+", default=None, help="gallery names left out of the ranking")
+    q.add_argument("--exclude-reference", action="store_true", help="leave the reference out when it is a gallery name")
     common(q)
+    ad = sub.add_parser("add", help="encode the image files whose stem is not yet a name of the store and append them")
+    ad.add_argument("--index", type=str, required=True)
+    ad.add_argument("--images", type=str, required=True, help="directory of image files; a file's stem is its gallery name")
+    ad.add_argument("--out", type=str, default=None, help="write here instead of rewriting --index")
+    common(ad)
+    rm = sub.add_parser("remove", help="drop named rows from a store")
+    rm.add_argument("--index", type=str, required=True)
+    rm.add_argument("--names", type=str, nargs="+", required=True)
+    rm.add_argument("--out", type=str, default=None, help="write here instead of rewriting --index")
     return p
 
 
@@ -207,7 +391,15 @@ def query_index(a) -> List[Tuple[str, float]]:
     model, _ = _load(MODEL_NAME, a.backbone, a.model_path, a.dtype, a.vit_depth)
     s = Searcher(model, a.index, preprocess=_preprocess(a.gpu_preprocess, model.device)[0])
     timings = {} if a.json else None
-    hits = s.search([a.reference if a.reference is not None else Path(a.reference_image)], [a.caption], k=a.k, timings=timings)[0]
+    within = None
+    if a.within_file is not None:
+        within = [l.strip() for l in Path(a.within_file).read_text().splitlines() if l.strip()]
+    elif a.within_glob is not None:
+        within = [n for n in s.names if fnmatch.fnmatchcase(n, a.within_glob)]
+        if not within:
+            raise ValueError(f"--within-glob {a.within_glob!r} matches no gallery name")
+    hits = s.search([a.reference if a.reference is not None else Path(a.reference_image)], [a.caption], k=a.k, timings=timings,
+                    within=within, exclude=a.exclude, exclude_reference=a.exclude_reference)[0]
     if a.json:
         print(json.dumps({"caption": a.caption, "reference": a.reference or a.reference_image, "timings": timings,
                           "results": [{"rank": r + 1, "name": n, "score": v} for r, (n, v) in enumerate(hits)]}))
@@ -217,9 +409,47 @@ def query_index(a) -> List[Tuple[str, float]]:
     return hits
 
 
+def add_to_index(a) -> dict:
+    """Encode the files under --images whose stem the store does not hold yet and append them (`index.append_index`)."""
+    from .blip_validate import _load, _preprocess, model_fingerprint
+    from .data_utils import ImageDirDataset
+    from .harness import extract_index_blip_features
+    from .index import _read_store, append_index
+    _, old_raw, old_names, _, meta = _read_store(a.index)
+    model, _ = _load(MODEL_NAME, a.backbone, a.model_path, a.dtype, a.vit_depth)
+    fp = model_fingerprint(model)
+    if meta.get("checkpoint_sha256") != fp:
+        raise ValueError(f"{a.index}: written by another checkpoint ({str(meta.get('checkpoint_sha256', '?'))[:16]}, this model is {fp[:16]})")
+    preprocess, workers = _preprocess(a.gpu_preprocess, model.device)
+    dataset = ImageDirDataset(a.images, preprocess)
+    have = set(old_names)
+    new = [i for i, n in enumerate(dataset.names) if n not in have]
+    dataset.paths, dataset.names = [dataset.paths[i] for i in new], [dataset.names[i] for i in new]
+    total = len(old_names)
+    if new:
+        keep = old_raw is not None
+        (feats, raw), names = extract_index_blip_features(dataset, model, num_workers=workers if len(dataset) >= 256 else 0, keep_raw=keep)
+        if len(names) != len(dataset):
+            raise SystemExit(f"search add: {len(dataset) - len(names)} of {len(dataset)} files could not be read")
+        total = append_index(a.index, names, feats, raw=raw if keep else None, checkpoint_sha256=fp, out=a.out)
+    elif a.out is not None:
+        total = append_index(a.index, [], torch.empty((0, 32, 256)), checkpoint_sha256=fp, out=a.out)
+    out = {"index": str(a.out or a.index), "added": len(new), "images": total}
+    print(json.dumps(out))
+    return out
+
+
+def remove_from_store(a) -> dict:
+    from .index import remove_from_index
+    total = remove_from_index(a.index, a.names, out=a.out)
+    out = {"index": str(a.out or a.index), "removed": len(set(a.names)), "images": total}
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     a = _parser().parse_args(argv)
-    return build_index(a) if a.command == "build" else query_index(a)
+    return {"build": build_index, "query": query_index, "add": add_to_index, "remove": remove_from_store}[a.command](a)
 
 
 if __name__ == "__main__":

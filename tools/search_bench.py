@@ -16,7 +16,20 @@ of (a) and (b), and for (a1) / (d) the bytes / s.
     python tools/search_bench.py --query-split [--sizes 123403] [--reps 10]
 
 Report only: one whole `Searcher` query on the full-depth synthetic ViT-g model (fp16 engine), split into reference embeddings (a stored
-name: a lookup; an image file: decode + transform + ViT), fuse and rank, each phase ended by a device synchronisation."""
+name: a lookup; an image file: decode + transform + ViT), fuse and rank, each phase ended by a device synchronisation.
+
+    python tools/search_bench.py --filter [--sizes 123403,1000000] [--nq 1,32,64,256] [-k 50] [--reps 20] [--warmup 3] [--out FILE]
+
+The filtered search against what there is without it, same protocol, for row lists of M = N (the identity list), N - 100, N / 3,
+N / 100 and 1000 random ascending rows:
+
+  (r) rows     E.search_topk(rows=): sprc_sim_max_stream_rows on the listed images + two-level top-k on M scores
+  (r1) ..sim   its score kernel alone -> the achieved bytes / s of the listed images
+  (p) plain    E.search_topk without a list: what any query costs without the filter (it cannot filter)
+  (g) gather   feats.index_select(0, rows) + E.search_topk on the copy, the copy timed: the filter without the kernel
+               (its indices are positions in the copy)
+  (g+) ..map   the same with the positions mapped back to gallery rows: what a caller of (g) has to run to get what (r) returns
+  (m) mask     above 32 queries only: E.sim_max (GEMM) on the whole gallery + -inf on the unlisted columns + E.topk_segmented"""
 import argparse
 import statistics
 import sys
@@ -102,9 +115,63 @@ def query_split(a, say):
                     f"(medians of {a.reps}; host wall time per phase, device idle at each boundary)")
 
 
+def _gather_search(q16, g16, rows64, rows, k):
+    """arm (g) finished: the copy's positions mapped back to gallery rows, as (r) returns them"""
+    v, i = E.search_topk(q16, g16.index_select(0, rows64), k)
+    return v, torch.where(i < 0, i, rows[i.clamp(min=0)])
+
+
+def filter_bench(a, say):
+    dev = "cuda:0"
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N in [int(x) for x in a.sizes.split(",")]:
+        g16 = _gallery(N, gen, dev)
+        say(f"\nN = {N}  ({g16.numel() * 2 / 2**20:.0f} MiB fp16)")
+        perm = torch.randperm(N, generator=gen, device=dev)
+        lists = [("N (identity)", torch.arange(N, device=dev))] + [(what, perm[:m].sort().values) for what, m in
+                 (("N - 100", N - 100), ("N / 3", N // 3), ("N / 100", N // 100), ("1000", min(1000, N)))]
+        for nq in [int(x) for x in a.nq.split(",")]:
+            q16 = _unit(torch.randn((nq, 256), generator=gen, device=dev)).to(torch.float16).contiguous()
+            for what, rows64 in lists:
+                rows = rows64.to(torch.int32).contiguous()
+                M = rows.shape[0]
+                sim_r = torch.empty((nq, M), dtype=torch.float32, device=dev)
+                arms = {
+                    "r": lambda: E.search_topk(q16, g16, a.k, rows=rows),
+                    "p": lambda: E.search_topk(q16, g16, a.k),
+                    "g": lambda: E.search_topk(q16, g16.index_select(0, rows64), a.k),
+                    "g+": lambda: _gather_search(q16, g16, rows64, rows, a.k),
+                    "r1": lambda: E.sim_max_stream(q16, g16, out=sim_r, rows=rows),
+                }
+                if nq > 32:
+                    sim_m = E.segmented_sim_buffer(nq, N, dev)
+                    off = torch.full((N,), float("-inf"), dtype=torch.float32, device=dev)
+                    off[rows64] = 0.0
+                    arms["m"] = lambda: E.topk_segmented(E.sim_max(q16, g16, out=sim_m).add_(off), a.k)
+                t = _time(arms, a.reps, a.warmup)
+                vr, ir = E.search_topk(q16, g16, a.k, rows=rows)
+                vg, ig = _gather_search(q16, g16, rows64, rows, a.k)
+                assert torch.equal(ir, ig) and ir.dtype == ig.dtype and torch.equal(vr, vg)
+                med = {n: statistics.median(x) for n, x in t.items()}
+                spread = {n: max(x) - min(x) for n, x in t.items()}
+                seg, S = E.search_segments(nq, M)
+                line = (f"  nq={nq:4d} M={M:8d} [{what:>12s}] S={S:3d}  (r) rows {_fmt(t['r'])}   (p) plain {_fmt(t['p'])}   (g) gather {_fmt(t['g'])}   (g+) gather+map {_fmt(t['g+'])}"
+                        + (f"   (m) gemm+mask {_fmt(t['m'])}" if "m" in t else ""))
+                say(line)
+                say(f"           r/g = {med['r'] / med['g']:5.2f} (spread of the two {max(spread['r'], spread['g']) * 1e3:7.1f} us)   r/g+ = {med['r'] / med['g+']:5.2f} "
+                    f"(spread {max(spread['r'], spread['g+']) * 1e3:7.1f} us)   r/p = {med['r'] / med['p']:5.2f} "
+                    f"(spread {max(spread['r'], spread['p']) * 1e3:7.1f} us)"
+                    + (f"   r/m = {med['r'] / med['m']:5.2f} (spread {max(spread['r'], spread['m']) * 1e3:7.1f} us)" if "m" in t else "")
+                    + f"   (r1) rows kernel {_fmt(t['r1'])} = {M * 16384 * -(-nq // 32) / med['r1'] / 1e9:6.2f} TB/s of listed images")
+                del sim_r
+        del g16, perm, lists
+        torch.cuda.empty_cache()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--query-split", action="store_true")
+    p.add_argument("--filter", action="store_true")
     p.add_argument("--sizes", default="2297,123403,1000000")
     p.add_argument("--nq", default="1,8,32,64,256")
     p.add_argument("-k", type=int, default=50)
@@ -122,9 +189,10 @@ def main(argv=None):
 
     say(f"search_bench: k={a.k} reps={a.reps} warmup={a.warmup}  device={torch.cuda.get_device_name(0)}  times in us: median [min .. max]")
     say(f"clocks: {_clock()}")
-    if a.query_split:
-        query_split(a, say)
+    if a.query_split or a.filter:
+        (query_split if a.query_split else filter_bench)(a, say)
         if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
             Path(a.out).write_text("\n".join(lines) + "\n")
         return lines
     gen = torch.Generator(device=dev).manual_seed(0)
