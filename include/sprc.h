@@ -264,6 +264,15 @@ int sprc_sim_max_stream(const void* fusion, const void* feats, float* sim, int64
 int sprc_sim_max_stream_rows(const void* fusion, const void* feats, const int32_t* rows, float* sim, int64_t ld_sim,
                              int32_t nq, int32_t M, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
 
+/* sprc_sim_max_stream_rows with a per-query filter: sim[q, m] = max_j <fusion[q,:], feats[rows[m], j, :]> if (admit[m] >> q) & 1, else
+ * -inf, for q < nq and m in [0, M).  admit: DEVICE uint32 [M], one word per list position, bit q for query q of this launch; bits at or
+ * above nq are ignored.  The contract is sprc_sim_max_stream_rows's plus admit != NULL and 4-byte aligned; anything else is SPRC_EINVAL
+ * before any launch.  Every element of sim[q < nq, 0..M) is written, as a score or -inf, and nothing else; allocates nothing, does not
+ * synchronise.  An admitted score is bit-identical to sprc_sim_max_stream's sim[q, rows[m]] for any data, list order and admit word.
+ * Same ABI version: a symbol added, nothing changed. */
+int sprc_sim_max_stream_admit(const void* fusion, const void* feats, const int32_t* rows, const uint32_t* admit, float* sim, int64_t ld_sim,
+                              int32_t nq, int32_t M, int32_t N, int32_t E, int32_t dtype, sprc_stream s);
+
 /* Per row of sim[nq,N] (ld in elements): the k smallest keys (fl32(1 - sim[n]), gidx[n]) ascending,
  * i.e. the first k entries of a STABLE argsort of the fp32 distance (the ranking contract,
  * SURVEY.md section 7).  gidx: optional int32 [nq,N] global indices (NULL -> n + idx_base).

@@ -148,6 +148,7 @@ SIGNATURES = {
     "sprc_sim_max": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "sprc_sim_max_stream": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "sprc_sim_max_stream_rows": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "sprc_sim_max_stream_admit": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     "sprc_topk": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
     "sprc_topk_wide": (i32, [vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
     "sprc_rank_of": (i32, [vp, i64, vp, i32, i32, i32, vp, vp]),

@@ -1,4 +1,5 @@
-// search.hip -- index search: streaming small-batch scoring (sprc_sim_max_stream) and its row-list form (sprc_sim_max_stream_rows).
+// search.hip -- index search: streaming small-batch scoring (sprc_sim_max_stream), its row-list form (sprc_sim_max_stream_rows)
+// and the row-list form with a per-query admit mask (sprc_sim_max_stream_admit).
 //
 // sim[q, n] = max_j <fusion[q,:], feats[n,j,:]> for 1 <= nq <= 32 queries against a gallery that is read from HBM exactly once:
 // 16 KiB per image (16-bit), 2 * 32 * 256 * nq flops per image -- at nq = 1 almost no arithmetic per byte.  sprc_sim_max runs this
@@ -150,6 +151,61 @@ __global__ __launch_bounds__(256, 2) void sim_max_stream_rows_kernel(const char*
     if (r < nq && m + h < M) out[m] = h ? m1 : m0;
 }
 
+// ---- the row-list walk with a per-query filter (sprc_sim_max_stream_admit): bit q of admit[m] admits image rows[m] for query q ---------
+// Query q sits on lane column r = q and lane (r, h) stores position m + h of its pair, so the filter is one word per lane, admit[m + h],
+// and one bit test at the store: an admitted score is the rows kernel's value (the same stream_dot chain on the same operands), any
+// other element of sim[q < nq, 0..M) is -inf.  The store stays unconditional for r < nq && m + h < M and there is still one store
+// instruction per pair.  The word of trip t + 1 is fetched at the top of trip t, next to the row indices and ahead of the trip's operand
+// loads in the same in-order vmcnt queue: by the time trip t + 1 stores, its MFMAs have already waited for younger loads, so the word
+// costs no wait of its own and never sits between an MFMA chain and the loads behind it.  Like the row indices it is a relaxed
+// wave-scope atomic load with the position clamped to M - 1 (see stream_row_ahead: a plain load is sunk to the loop's end and waited
+// for at once).  Bits at or above nq belong to lanes that store nothing.
+__device__ __forceinline__ uint32_t stream_admit_ahead(const uint32_t* admit, int m, int M) {
+    return __hip_atomic_load(admit + min(m, M - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void sim_max_stream_admit_kernel(const char* __restrict__ fusion, const char* __restrict__ feats,
+                                                                      const int32_t* __restrict__ rows, const uint32_t* __restrict__ admit,
+                                                                      float* __restrict__ sim, int64_t ld, int nq, int M, int N, int trips) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    u32x4 q[16];
+    {
+        const u32x4* p = reinterpret_cast<const u32x4*>(fusion + (int64_t)min(r, nq - 1) * (STREAM_E * 2) + h * 16);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const u32x4 v = p[2 * t];
+            q[t] = r < nq ? v : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    const int t0 = (int)((int64_t)blockIdx.x * trips / gridDim.x), t1 = (int)((int64_t)(blockIdx.x + 1) * trips / gridDim.x);
+    if (t0 >= t1) return;
+    const int lane_off = r * (STREAM_E * 2) + h * 16;
+    float* out = sim + (int64_t)r * ld + h;          // lane (r, h) stores position m + h of its pair
+    int m = t0 * STREAM_P + 2 * wave;                // first list position of this wave's pair in the current trip
+    u32x4 a0[16], a1[16];
+    stream_load_row(a0, feats, lane_off, stream_row_clamp(rows[min(m, M - 1)], N));
+    stream_load_row(a1, feats, lane_off, stream_row_clamp(rows[min(m + 1, M - 1)], N));
+    int n0 = rows[min(m + STREAM_P, M - 1)], n1 = rows[min(m + STREAM_P + 1, M - 1)];      // the next trip's rows, as fetched
+    uint32_t w = admit[min(m + h, M - 1)];                                                  // this trip's admit word of the lane
+    const float none = -__builtin_inff();
+    for (int trip = t0; trip + 1 < t1; ++trip, m += STREAM_P) {
+        const int j0 = stream_row_clamp(n0, N), j1 = stream_row_clamp(n1, N);                // fetched a trip ago
+        n0 = stream_row_ahead(rows, m + 2 * STREAM_P, M), n1 = stream_row_ahead(rows, m + 2 * STREAM_P + 1, M);
+        const uint32_t wn = stream_admit_ahead(admit, m + STREAM_P + h, M);                  // used by the next trip's store
+        const f32x16 c0 = stream_dot<F16>(a0, q);
+        stream_load_row(a0, feats, lane_off, j0);
+        const f32x16 c1 = stream_dot<F16>(a1, q);
+        stream_load_row(a1, feats, lane_off, j1);
+        const float m0 = stream_rowmax(c0), m1 = stream_rowmax(c1);
+        if (r < nq && m + h < M) out[m] = (w >> r) & 1u ? (h ? m1 : m0) : none;
+        w = wn;
+    }
+    const float m0 = stream_rowmax(stream_dot<F16>(a0, q)), m1 = stream_rowmax(stream_dot<F16>(a1, q));
+    if (r < nq && m + h < M) out[m] = (w >> r) & 1u ? (h ? m1 : m0) : none;
+}
+
 }  // namespace sprc
 
 using namespace sprc;
@@ -198,5 +254,30 @@ extern "C" int sprc_sim_max_stream_rows(const void* fusion, const void* feats, c
     else
         hipLaunchKernelGGL(sim_max_stream_rows_kernel<false>, dim3(grid), dim3(256), 0, st, f, g, rows, sim, ld_sim, nq, M, N, trips);
     SPRC_CHECK_LAUNCH("sprc_sim_max_stream_rows");
+    return SPRC_OK;
+}
+
+extern "C" int sprc_sim_max_stream_admit(const void* fusion, const void* feats, const int32_t* rows, const uint32_t* admit, float* sim,
+                                         int64_t ld_sim, int32_t nq, int32_t M, int32_t N, int32_t E, int32_t dtype, sprc_stream s) {
+    SPRC_REQUIRE(fusion && feats && rows && admit && sim, "sprc_sim_max_stream_admit: null pointer");
+    SPRC_REQUIRE(nq >= 1 && nq <= 32, "sprc_sim_max_stream_admit: nq=%d must be in [1,32] (walk more queries in blocks of 32)", nq);
+    SPRC_REQUIRE(E == STREAM_E, "sprc_sim_max_stream_admit: E=%d must be %d", E, STREAM_E);
+    SPRC_REQUIRE(dtype == SPRC_F16 || dtype == SPRC_BF16, "sprc_sim_max_stream_admit: dtype %d must be SPRC_F16 or SPRC_BF16", dtype);
+    SPRC_REQUIRE(N >= 1 && M >= 1 && M <= INT32_MAX - 4 * STREAM_P && ld_sim >= M, "sprc_sim_max_stream_admit: bad shape M=%d N=%d ld_sim=%lld", M, N,
+                 (long long)ld_sim);
+    SPRC_REQUIRE(((uintptr_t)fusion & 15) == 0 && ((uintptr_t)feats & 15) == 0 && ((uintptr_t)rows & 3) == 0 && ((uintptr_t)admit & 3) == 0,
+                 "sprc_sim_max_stream_admit: fusion and feats must be 16-byte aligned, rows and admit 4-byte aligned");
+    hipStream_t st = (hipStream_t)s;
+    const int trips = (int)(((int64_t)M + STREAM_P - 1) / STREAM_P);
+    const int grid = min(trips, STREAM_WG_PER_CU * stream_cus(st));
+    ProfScope prof(SPRC_K_RANK, st, 2.0 * nq * (double)M * 32.0 * E,
+                   (double)M * (STREAM_IMG_BYTES + 8) + (double)nq * E * 2.0 + (double)nq * M * 4.0);
+    const char* f = (const char*)fusion;
+    const char* g = (const char*)feats;
+    if (dtype == SPRC_F16)
+        hipLaunchKernelGGL(sim_max_stream_admit_kernel<true>, dim3(grid), dim3(256), 0, st, f, g, rows, admit, sim, ld_sim, nq, M, N, trips);
+    else
+        hipLaunchKernelGGL(sim_max_stream_admit_kernel<false>, dim3(grid), dim3(256), 0, st, f, g, rows, admit, sim, ld_sim, nq, M, N, trips);
+    SPRC_CHECK_LAUNCH("sprc_sim_max_stream_admit");
     return SPRC_OK;
 }

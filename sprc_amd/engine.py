@@ -235,11 +235,14 @@ STREAM_MAX_NQ = 32          # queries of one launch (the columns of one MFMA til
 
 
 def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torch.Tensor] = None,
-                   rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   rows: Optional[torch.Tensor] = None, admit: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`sim_max` for few queries against a stored 16-bit gallery (sprc_sim_max_stream: the gallery is streamed from HBM once, no
     LDS); fusion [nq,256], feats [N,32,256], both fp16 or both bf16.  More than 32 queries are walked in blocks of 32 into one sim.
     rows (optional): int32 device tensor [M] of gallery rows -> the COMPACT scores [nq, M], column m the score of image rows[m]
-    (sprc_sim_max_stream_rows: only the listed images are read; bit-identical to the columns `rows` of the call without it)."""
+    (sprc_sim_max_stream_rows: only the listed images are read; bit-identical to the columns `rows` of the call without it).
+    admit (optional, needs rows): int32 device tensor [ceil(nq / 32), M], contiguous, holding the bit patterns of uint32 words (bit 31
+    is the sign bit): bit i of word [b, m] admits image rows[m] for query 32 b + i.  Block b of queries is one
+    sprc_sim_max_stream_admit launch on row b; an admitted score has the bits it has without `admit`, every other one is -inf."""
     lib = L.load()
     nq, E = fusion.shape
     N, J, E2 = feats.shape
@@ -248,6 +251,12 @@ def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torc
     if rows is not None:
         assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.device == feats.device
     W = N if rows is None else rows.shape[0]
+    if admit is not None:
+        if rows is None:
+            raise ValueError("sim_max_stream: admit requires rows")
+        if admit.dtype != torch.int32 or tuple(admit.shape) != (-(-nq // STREAM_MAX_NQ), W) or not admit.is_contiguous() or admit.device != feats.device:
+            raise ValueError(f"sim_max_stream: admit must be a contiguous int32 device tensor [{-(-nq // STREAM_MAX_NQ)}, {W}], got "
+                             f"{admit.dtype} {tuple(admit.shape)}")
     if out is None:
         out = torch.empty((nq, W), dtype=torch.float32, device=fusion.device)
     assert out.dtype == torch.float32 and out.shape == (nq, W) and (W == 1 or out.stride(1) == 1)
@@ -256,9 +265,12 @@ def sim_max_stream(fusion: torch.Tensor, feats: torch.Tensor, out: Optional[torc
         if rows is None:
             L.check(lib.sprc_sim_max_stream(fusion[q0:].data_ptr(), feats.data_ptr(), out[q0:].data_ptr(), out.stride(0), nb, N, E, dt,
                                             _stream()), "sprc_sim_max_stream")
-        else:
+        elif admit is None:
             L.check(lib.sprc_sim_max_stream_rows(fusion[q0:].data_ptr(), feats.data_ptr(), rows.data_ptr(), out[q0:].data_ptr(), out.stride(0),
                                                  nb, W, N, E, dt, _stream()), "sprc_sim_max_stream_rows")
+        else:
+            L.check(lib.sprc_sim_max_stream_admit(fusion[q0:].data_ptr(), feats.data_ptr(), rows.data_ptr(), admit[q0 // STREAM_MAX_NQ].data_ptr(),
+                                                  out[q0:].data_ptr(), out.stride(0), nb, W, N, E, dt, _stream()), "sprc_sim_max_stream_admit")
     return out
 
 
@@ -317,7 +329,7 @@ def topk_segmented(sim: torch.Tensor, k: int, S: Optional[int] = None) -> Tuple[
 
 
 def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Optional[int] = None, rows: Optional[torch.Tensor] = None,
-                exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                exclude: Optional[torch.Tensor] = None, admit: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Index search: the k best gallery rows for each query -> (vals [nq,k] fp32, idx [nq,k] int32), 1 <= k <= 256; the streaming
     score kernel followed by the two-level top-k.  The result is bit-identical to `topk` / `topk_wide` on `sim_max_stream`'s scores
     for every S (default: `search_segments`).
@@ -328,11 +340,15 @@ def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Option
     validated where it is made (`search.resolve_rows`), not here: a tensor handed to this function is trusted.
     exclude: int32 tensor [nq] of gallery rows, negative for none -- that row's score is set to -inf for that query on the device
     before the top-k (at its compact position when `rows` is given; a row that is not listed excludes nothing).
-    With either argument, positions beyond the number of admissible images come back as score -inf and index -1 for every S.
-    With neither, the function does exactly what it did without them."""
+    admit (needs rows): per-query filters as `sim_max_stream` takes them, int32 [ceil(nq / 32), M] -- query 32 b + i ranks the images
+    rows[m] whose word [b, m] has bit i set; every other score is -inf before the top-k.  `exclude` may be combined with it.
+    With any of these arguments, positions beyond the number of admissible images come back as score -inf and index -1 for every S.
+    With none, the function does exactly what it did without them."""
     if not 1 <= k <= 256:
         raise ValueError(f"search_topk: k={k} must be in [1,256]")
     nq, N = fusion16.shape[0], feats16.shape[0]
+    if admit is not None and rows is None:
+        raise ValueError("search_topk: admit requires rows")
     if rows is None and exclude is None:
         sim = segmented_sim_buffer(nq, N, fusion16.device, S)
         sim_max_stream(fusion16, feats16, out=sim)
@@ -342,7 +358,7 @@ def search_topk(fusion16: torch.Tensor, feats16: torch.Tensor, k: int, S: Option
     if M < 1:
         raise ValueError("search_topk: an empty row list")
     sim = segmented_sim_buffer(nq, M, dev, S)
-    sim_max_stream(fusion16, feats16, out=sim, rows=rows)
+    sim_max_stream(fusion16, feats16, out=sim, rows=rows, admit=admit)
     if exclude is not None:
         exclude = exclude.to(device=dev, dtype=torch.int32)
         if exclude.shape != (nq,):

@@ -29,7 +29,18 @@ N / 100 and 1000 random ascending rows:
   (g) gather   feats.index_select(0, rows) + E.search_topk on the copy, the copy timed: the filter without the kernel
                (its indices are positions in the copy)
   (g+) ..map   the same with the positions mapped back to gallery rows: what a caller of (g) has to run to get what (r) returns
-  (m) mask     above 32 queries only: E.sim_max (GEMM) on the whole gallery + -inf on the unlisted columns + E.topk_segmented"""
+  (m) mask     above 32 queries only: E.sim_max (GEMM) on the whole gallery + -inf on the unlisted columns + E.topk_segmented
+
+    python tools/search_bench.py --per-query [--sizes 123403,1000000] [--nq 1,8,32] [-k 50] [--reps 20] [--warmup 3] [--out FILE]
+
+Per-query filters against what there is without them, same protocol: every query has its own random ascending list of N / 100 or
+N / 3 rows, or the whole gallery minus 100 rows of its own; one more row gives every query the whole gallery (all-ones words: the
+price of the bit test alone).  The union of the lists is what (q) and (u) walk.
+
+  (q) admit    one E.search_topk(rows=union, admit=): sprc_sim_max_stream_admit + two-level top-k on the union's scores
+  (s) serial   nq E.search_topk(rows=list_b) calls of one query each: per-query filters without the kernel
+  (u) union    E.search_topk(rows=union) without admit: what the mask costs (it cannot filter per query)
+  (q1) ..sim   the admit kernel alone -> the achieved bytes / s of the listed images"""
 import argparse
 import statistics
 import sys
@@ -168,18 +179,79 @@ def filter_bench(a, say):
         torch.cuda.empty_cache()
 
 
+def _per_query_lists(N, nq, m, minus, gen, dev):
+    """nq ascending int32 row lists: m random rows each, or (minus) all rows but m random ones; m = None: all rows."""
+    out = []
+    for _ in range(nq):
+        if m is None:
+            out.append(torch.arange(N, device=dev, dtype=torch.int32))
+            continue
+        perm = torch.randperm(N, generator=gen, device=dev)
+        out.append((perm[m:] if minus else perm[:m]).sort().values.to(torch.int32).contiguous())
+    return out
+
+
+def per_query_bench(a, say):
+    dev = "cuda:0"
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N in [int(x) for x in a.sizes.split(",")]:
+        g16 = _gallery(N, gen, dev)
+        say(f"\nN = {N}  ({g16.numel() * 2 / 2**20:.0f} MiB fp16)")
+        for nq in [int(x) for x in a.nq.split(",")]:
+            if not 1 <= nq <= 32:
+                raise SystemExit("--per-query: one block of queries, nq in 1 .. 32")
+            q16 = _unit(torch.randn((nq, 256), generator=gen, device=dev)).to(torch.float16).contiguous()
+            for what, m, minus in (("N / 100 each", N // 100, False), ("N / 3 each", N // 3, False), ("N - 100 each", 100, True), ("N each (ones)", None, False)):
+                lists = _per_query_lists(N, nq, m, minus, gen, dev)
+                bits = torch.zeros(N, dtype=torch.int64, device=dev)
+                for b, rows_b in enumerate(lists):
+                    bits[rows_b.long()] |= 1 << b
+                union64 = torch.nonzero(bits).flatten()
+                union = union64.to(torch.int32).contiguous()
+                w = bits[union64]
+                admit = torch.where(w >= 2**31, w - 2**32, w).to(torch.int32).view(1, -1).contiguous()
+                M = union.shape[0]
+                sim_q = torch.empty((nq, M), dtype=torch.float32, device=dev)
+                qs = [q16[b:b + 1].contiguous() for b in range(nq)]
+                arms = {
+                    "q": lambda: E.search_topk(q16, g16, a.k, rows=union, admit=admit),
+                    "s": lambda: [E.search_topk(qs[b], g16, a.k, rows=lists[b]) for b in range(nq)],
+                    "u": lambda: E.search_topk(q16, g16, a.k, rows=union),
+                    "q1": lambda: E.sim_max_stream(q16, g16, out=sim_q, rows=union, admit=admit),
+                }
+                t = _time(arms, a.reps, a.warmup)
+                vq, iq = E.search_topk(q16, g16, a.k, rows=union, admit=admit)
+                for b in range(nq):
+                    vs, js = E.search_topk(qs[b], g16, a.k, rows=lists[b])
+                    assert torch.equal(iq[b:b + 1], js) and torch.equal(vq[b:b + 1], vs)
+                med = {n: statistics.median(x) for n, x in t.items()}
+                spread = {n: max(x) - min(x) for n, x in t.items()}
+                qs_spread, qu_spread = max(spread["q"], spread["s"]), max(spread["q"], spread["u"])
+                ahead = med["s"] - med["q"]
+                say(f"  nq={nq:3d} [{what:>13s}] union M={M:8d} S={E.search_segments(nq, M)[1]:3d}  (q) admit {_fmt(t['q'])}   (s) serial {_fmt(t['s'])}   (u) union {_fmt(t['u'])}")
+                say(f"           s/q = {med['s'] / med['q']:6.2f}  ((q) ahead by {ahead * 1e3:9.1f} us; spread of the two arms {qs_spread * 1e3:7.1f} us: "
+                    f"{'ahead' if ahead > qs_spread else 'behind' if -ahead > qs_spread else 'level'})   q/u = {med['q'] / med['u']:5.2f} (spread {qu_spread * 1e3:7.1f} us)"
+                    f"   (q1) admit kernel {_fmt(t['q1'])} = {M * 16384 / med['q1'] / 1e9:6.2f} TB/s of listed images")
+                del sim_q, bits, lists, union, union64, admit
+        del g16
+        torch.cuda.empty_cache()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--query-split", action="store_true")
     p.add_argument("--filter", action="store_true")
-    p.add_argument("--sizes", default="2297,123403,1000000")
-    p.add_argument("--nq", default="1,8,32,64,256")
+    p.add_argument("--per-query", action="store_true")
+    p.add_argument("--sizes", default=None, help="default 2297,123403,1000000; --per-query: 123403,1000000")
+    p.add_argument("--nq", default=None, help="default 1,8,32,64,256; --per-query: 1,8,32")
     p.add_argument("-k", type=int, default=50)
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--fp32-budget-gb", type=float, default=40.0)
     p.add_argument("--out", default=None)
     a = p.parse_args(argv)
+    a.sizes = a.sizes or ("123403,1000000" if a.per_query else "2297,123403,1000000")
+    a.nq = a.nq or ("1,8,32" if a.per_query else "1,8,32,64,256")
     dev = "cuda:0"
     lines = []
 
@@ -189,8 +261,8 @@ def main(argv=None):
 
     say(f"search_bench: k={a.k} reps={a.reps} warmup={a.warmup}  device={torch.cuda.get_device_name(0)}  times in us: median [min .. max]")
     say(f"clocks: {_clock()}")
-    if a.query_split or a.filter:
-        (query_split if a.query_split else filter_bench)(a, say)
+    if a.query_split or a.filter or a.per_query:
+        (query_split if a.query_split else filter_bench if a.filter else per_query_bench)(a, say)
         if a.out:
             Path(a.out).parent.mkdir(parents=True, exist_ok=True)
             Path(a.out).write_text("\n".join(lines) + "\n")
