@@ -57,7 +57,8 @@ typedef void* sprc_stream;                    /* hipStream_t */
 
 /* Row indirection shared by GEMM / LayerNorm: logical row m lives at physical row
  *   (m / rows_per_group) * group_stride + (m % rows_per_group) + group_offset
- * (rows_per_group == 0 -> identity).  Lets the Q-Former address "rows [:32]" / "rows [32:]" of a
+ * (rows_per_group == 0 -> identity; a power of two otherwise, group_stride and group_offset >= 0: sprc_gemm answers a negative
+ * field with SPRC_EUNSUPPORTED).  Lets the Q-Former address "rows [:32]" / "rows [32:]" of a
  * [B,64,768] tensor (Qformer.py:436,455-468) without copies. */
 typedef struct { int32_t rows_per_group, group_stride, group_offset; } sprc_rowmap;
 

@@ -21,6 +21,7 @@ static int gemm_impl(const sprc_gemm_args* a, const sprc_gemm_args* b, sprc_stre
                  "sprc_gemm(k8): a split-precision product takes fp16 operands, K %% 128 == 0, k8 %% 128 == 0, k8 >= 512, lda / ldw >= K + k8 / 2, no max32");
     SPRC_REQUIRE(a->dtype != SPRC_FP8 || (a->w_scale != nullptr && a->a_scale > 0.f && !a->max32 && b == nullptr),
                  "sprc_gemm(fp8): needs w_scale, a_scale > 0; no max32 / paired launch");
+    SPRC_REQUIRE(a->dtype != SPRC_FP8 || ((uintptr_t)a->w_scale % 16) == 0, "sprc_gemm(fp8): w_scale must be 16-byte aligned (the epilogue loads it as 4-float vectors)");
     SPRC_REQUIRE(a->out_dtype != SPRC_FP8 || a->out_scale > 0.f, "sprc_gemm: SPRC_FP8 output needs out_scale > 0");
     SPRC_REQUIRE(a->out_dtype != SPRC_F16 || a->dtype == SPRC_F16 ||
                      ((a->dtype == SPRC_BF16 || a->dtype == SPRC_FP8) && a->act == SPRC_ACT_NONE && !a->resid && !a->max32),
@@ -45,6 +46,12 @@ static int gemm_impl(const sprc_gemm_args* a, const sprc_gemm_args* b, sprc_stre
     p.c_shift = ilog2_exact(a->cmap.rows_per_group); p.c_stride = a->cmap.group_stride; p.c_off = a->cmap.group_offset;
     if (p.a_shift == -2 || p.c_shift == -2) {
         set_error("sprc_gemm: rows_per_group must be a power of two");
+        return SPRC_EUNSUPPORTED;
+    }
+    // a negative stride or offset makes a tile-relative row offset negative: the kernels form it as an unsigned 32-bit value
+    if ((p.a_shift >= 0 && (p.a_stride < 0 || p.a_off < 0)) || (p.c_shift >= 0 && (p.c_stride < 0 || p.c_off < 0)) ||
+        (b != nullptr && ((p.a_shift >= 0 && b->amap.group_offset < 0) || (p.c_shift >= 0 && b->cmap.group_offset < 0)))) {
+        set_error("sprc_gemm: negative row-map field (amap: stride %d offset %d; cmap: stride %d offset %d)", p.a_stride, p.a_off, p.c_stride, p.c_off);
         return SPRC_EUNSUPPORTED;
     }
     if (!fits_u32(p)) {

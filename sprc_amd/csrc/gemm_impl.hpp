@@ -361,7 +361,12 @@ __device__ __forceinline__ float epi_value(float v, bool scaled, S scale, bool h
     if (has_bias) v += bias();
     if constexpr (ACT == SPRC_ACT_GELU) v = FAST_GELU ? gelu_fast(v) : gelu_erf(v);
     if constexpr (ACT == SPRC_ACT_QUICKGELU) v = FAST_QGELU ? quick_gelu_fast(v) : quick_gelu(v);
-    if (has_resid) v += resid();
+    if (has_resid) {
+        // The activation's last multiply stays a multiply: left to hipcc, it fused with this add in some instantiations and not in others (seen:
+        // the 8- and the 4-column store path of one kernel, and the scalar path, a last bit apart on act(x) + resid).  No instruction is emitted.
+        if constexpr (ACT != SPRC_ACT_NONE) asm("" : "+v"(v));
+        v += resid();
+    }
     if constexpr (std::is_same<OutT, fp8_t>::value) v *= out_scale;
     return v;
 }
